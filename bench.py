@@ -12,6 +12,11 @@ Launch (the driver does this):
       --master-addr 127.0.0.1 bench.py --gpus N --steps K --warmup W
 
 Rank 0 prints ONE JSON line with the whole-node aggregate.
+
+A plain run does only what that line needs: set up, warm up, time the K
+steps, print.  `--dump-outputs DIR` additionally writes what the last timed
+step computed (see `_dump_outputs`); `--full` additionally benches the
+secondary configs, each in a process of its own, before the flagship.
 """
 
 import argparse
@@ -37,11 +42,47 @@ def parse_args():
     p.add_argument("--dtype", type=str, default="bf16")
     p.add_argument("--full_rank", action="store_true",
                    help="bench full-rank training instead of ReLoRA")
-    p.add_argument("--suite", action="store_true",
+    p.add_argument("--full", "--suite", dest="full", action="store_true",
                    help="also bench the secondary configs (llama_250m r=128 "
                         "bs8, llama_7b r=256 bs4) before the flagship; one "
-                        "JSON line each, flagship printed LAST")
+                        "JSON line each, flagship printed LAST "
+                        "(--suite is the older name of this option)")
+    p.add_argument("--dump-outputs", dest="dump_outputs", type=str,
+                   default=None, metavar="DIR",
+                   help="after the timed steps, write what the last timed "
+                        "step computed to DIR/<name>.npy (float32)")
     return p.parse_args()
+
+
+# --dump-outputs size bounds: elements kept per trainable tensor and over all
+# of them (float32, so 12M elements = 48 MB, under the 64 MB a dump may take)
+_DUMP_PER_TENSOR = 16384
+_DUMP_TOTAL = 12 * 1024 * 1024
+
+
+def _dump_outputs(out_dir, loss, trainable):
+    """Write what a caller of the timed step receives from its LAST step:
+    the loss it returns (loss.npy, shape (1,)) and the trainable parameters
+    as the optimizer left them (params.npy, 1-D).  Tensors are taken in
+    parameter order and flattened; one with more than the per-tensor bound
+    contributes a fixed sample instead, drawn with a generator seeded by its
+    position, so two builds run with the same arguments write the same
+    elements in the same order."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"),
+            loss.detach().float().reshape(1).cpu().numpy())
+    cap = max(1, min(_DUMP_PER_TENSOR, _DUMP_TOTAL // max(1, len(trainable))))
+    parts = []
+    for i, p in enumerate(trainable):
+        flat = p.detach().reshape(-1)
+        if flat.numel() > cap:
+            g = torch.Generator(device="cpu").manual_seed(1000 + i)
+            idx = torch.randint(0, flat.numel(), (cap,), generator=g)
+            flat = flat[idx.to(flat.device)]
+        parts.append(flat.float().cpu())
+    np.save(os.path.join(out_dir, "params.npy"), torch.cat(parts).numpy())
 
 
 def main():
@@ -190,18 +231,28 @@ def main():
                          for t in step_ms) / len(step_ms)) ** 0.5, 2),
             },
         }
+        if args.dump_outputs:
+            _dump_outputs(args.dump_outputs, loss, trainable)
         print(json.dumps(result))
 
     if dist.is_initialized():
         dist.destroy_process_group()
 
 
-def _run_suite():
+def _run_full():
     """Secondary configs as subprocesses (fresh HIP context each), flagship
-    last so last-line JSON parsing still lands on the headline number."""
+    last so last-line JSON parsing still lands on the headline number.  The
+    secondary runs write no outputs: --dump-outputs is the flagship's."""
     import subprocess
     import sys
-    base = [a for a in sys.argv[1:] if a != "--suite"]
+    base, skip = [], False
+    for a in sys.argv[1:]:
+        if skip:
+            skip = False
+        elif a == "--dump-outputs":
+            skip = True
+        elif a not in ("--full", "--suite") and not a.startswith("--dump-outputs="):
+            base.append(a)
     for extra in (
         ["--model", "configs/llama_250m.json", "--batch_size", "8"],
         ["--model", "configs/llama_7b.json", "--batch_size", "4",
@@ -213,7 +264,7 @@ def _run_suite():
 
 if __name__ == "__main__":
     import sys
-    if "--suite" in sys.argv:
-        _run_suite()
+    if "--full" in sys.argv or "--suite" in sys.argv:
+        _run_full()
     else:
         main()
