@@ -310,11 +310,25 @@ class _HipFlashAttention(torch.autograd.Function):
         return dq, dk, dv, None
 
 
+def _attn_hip_supported(q):
+    """What the HIP attention kernels take: bf16, head_dim <= 128 and a
+    multiple of 8 (every row is read as 16-byte bf16x8 vectors).  Anything
+    else is SDPA's, by contract rather than by an error from inside the
+    extension.  Of the shipped configs that moves one: llama_40m has
+    head_dim 52 (416 / 8), whose rows are only 8-byte aligned; it used to
+    run the kernels on misaligned vector loads with no numerics test, and
+    now takes SDPA.  Every other config (head_dim 32, 48, 64, 80, 128)
+    stays on the HIP path."""
+    hd = q.shape[-1]
+    return q.dtype == torch.bfloat16 and hd <= 128 and hd % 8 == 0
+
+
 def flash_attention(q, k, v, causal=True, dropout_p=0.0, scale=None):
     """q,k,v: [B, nh, S, hd] -> [B, nh, S, hd]."""
     if scale is None:
         scale = q.shape[-1] ** -0.5
-    if causal and dropout_p == 0.0 and hip.use_hip(q, "attention"):
+    if (causal and dropout_p == 0.0 and _attn_hip_supported(q)
+            and hip.use_hip(q, "attention")):
         return _HipFlashAttention.apply(q, k, v, scale)
     return F.scaled_dot_product_attention(
         q, k, v, dropout_p=dropout_p, is_causal=causal, scale=scale
