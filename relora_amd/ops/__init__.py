@@ -4,7 +4,9 @@ from relora_amd.ops.functional import (  # noqa: F401
     gelu,
     fused_cross_entropy,
     layernorm,
+    lora_group_ok,
     lora_linear,
+    lora_linear_group,
     add_rmsnorm,
     rmsnorm,
     rmsnorm_torch,

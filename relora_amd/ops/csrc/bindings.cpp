@@ -40,6 +40,19 @@ void multi_tensor_scale_(std::vector<torch::Tensor> grads, double scale);
 std::vector<torch::Tensor> dropout_mask_fwd(torch::Tensor x, double p, int64_t seed);
 torch::Tensor dropout_mask_bwd(torch::Tensor dy, torch::Tensor mask, double p);
 void lora_add_nt_(torch::Tensor out, torch::Tensor P, torch::Tensor Q);
+std::vector<torch::Tensor> lora_down_dropout(torch::Tensor x, std::vector<torch::Tensor> As,
+                                             std::vector<int64_t> seeds, double p);
+// lora_group.cpp
+std::vector<torch::Tensor> lora_group_fwd(
+    torch::Tensor x, std::vector<torch::Tensor> Ws, std::vector<torch::Tensor> biases,
+    std::vector<torch::Tensor> As, std::vector<torch::Tensor> Bs,
+    std::vector<double> scales, std::vector<int64_t> seeds, double p,
+    std::vector<int64_t> fused);
+std::vector<torch::Tensor> lora_group_bwd(
+    std::vector<torch::Tensor> dys, torch::Tensor x, std::vector<torch::Tensor> masks,
+    std::vector<torch::Tensor> ts, std::vector<torch::Tensor> Ws,
+    std::vector<torch::Tensor> As, std::vector<torch::Tensor> bss,
+    std::vector<double> scales, double p);
 
 // fused_gemm.hip
 torch::Tensor fused_lora_gemm(torch::Tensor x, torch::Tensor w, torch::Tensor t,
@@ -91,6 +104,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dropout_mask_fwd", &dropout_mask_fwd, "fused dropout + packed mask (gfx950)");
   m.def("dropout_mask_bwd", &dropout_mask_bwd, "packed-mask dropout backward (gfx950)");
   m.def("lora_add_nt_", &lora_add_nt_, "out += P @ Q^T rank-r MFMA accumulate (gfx950)");
+  m.def("lora_down_dropout", &lora_down_dropout,
+        "t_g = dropout_g(x) @ A_g^T for up to 3 siblings, x read once (gfx950)");
+  m.def("lora_group_fwd", &lora_group_fwd,
+        "group LoRA linear forward for siblings sharing one input (gfx950)");
+  m.def("lora_group_bwd", &lora_group_bwd,
+        "group LoRA linear backward into one shared dx (gfx950)");
   m.def("fused_lora_gemm", &fused_lora_gemm,
         "y = x@W^T (+bias) + s*t@Bw^T fused MFMA GEMM, 256^2 glds tile (gfx950)");
   m.def("fused_lora_gemm3", &fused_lora_gemm3,

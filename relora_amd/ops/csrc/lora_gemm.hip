@@ -207,7 +207,10 @@ __global__ __launch_bounds__(256) void lora_skinny_kernel(
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int ldt = r + LPAD;
   __bf16* p_im = (__bf16*)smem;            // [128][ldt]
-  __bf16* q_im = p_im + 128 * ldt;         // [128][ldt]
+  // TRANSQ rows hold whole 64-element rotation blocks (trq_off permutes
+  // inside them), so their stride rounds r up to a multiple of 64
+  const int ldq_t = TRANSQ ? ((r + 63) & ~63) + LPAD : ldt;
+  __bf16* q_im = p_im + 128 * ldt;         // [128][ldt], TRANSQ: [128][ldq_t]
 
   const long m0 = (long)blockIdx.y * 128;
   const int n0 = blockIdx.x * 128;
@@ -253,7 +256,7 @@ __global__ __launch_bounds__(256) void lora_skinny_kernel(
       }
 #pragma unroll
       for (int j = 0; j < 8; ++j)
-        q_im[(nb + j) * ldt + trq_off(nb + j, k, r)] = v[j];
+        q_im[(nb + j) * ldq_t + trq_off(nb + j, k, r)] = v[j];
     }
   }
   __syncthreads();
@@ -281,7 +284,7 @@ __global__ __launch_bounds__(256) void lora_skinny_kernel(
         const int qrow = wc + ni * 16 + fr;
         const int koff = kk + kg;
         const bf16x8 b = *reinterpret_cast<const bf16x8*>(
-            TRANSQ ? q_im + qrow * ldt + trq_off(qrow, koff, r)
+            TRANSQ ? q_im + qrow * ldq_t + trq_off(qrow, koff, r)
                    : q_im + rm_idx(qrow, koff, ldt));
         acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc[mi][ni], 0, 0, 0);
       }
@@ -390,8 +393,8 @@ void lora_add_nn_(torch::Tensor out, torch::Tensor P, torch::Tensor Q,
   TORCH_CHECK(P.size(0) == M && Q.size(0) == r && Q.size(1) == N);
   TORCH_CHECK(r % 32 == 0 && r <= 256, "lora_add: r must be a multiple of 32, <=256");
   auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
-  const size_t lds = std::max<size_t>(2u * 128 * (r + LPAD), 128u * (128 + LPAD))
-                     * sizeof(__bf16);
+  const size_t lds = std::max<size_t>(128u * (r + LPAD) + 128u * (((r + 63) & ~63) + LPAD),
+                                      128u * (128 + LPAD)) * sizeof(__bf16);
   dim3 grid((N + 127) / 128, (M + 127) / 128), block(256);
   const bool has_mask = mask.defined() && mask.numel() > 0;
   if (has_mask) {
@@ -648,4 +651,252 @@ torch::Tensor dropout_mask_bwd(torch::Tensor dy, torch::Tensor mask, double p) {
                      mask.data_ptr<uint8_t>(), n8, n, inv_keep);
   HIP_CHECK_LAST();
   return dx;
+}
+
+// ---------------------------------------------------------------------------
+// lora_down_dropout: t_g[M,r] = dropout_g(x)[M,K] @ A_g[r,K]^T for G <= 3
+// sibling projections that share one input x (q/k/v, gate/up).  x is read
+// from HBM ONCE for the whole group; no [M,K] dropped copy is ever written.
+//
+// Block = 256 threads = 4 waves, 64 rows of x, all G*r output columns.
+// Wave w owns rows w*16..w*16+15, so in the 16x16x32 MFMA every lane's A
+// operand is exactly one aligned run of 8 consecutive k of one row: one
+// dropout_mask_kernel unit (one philox4 call, one mask byte).  The lane
+// loads that run straight from global into registers, derives each
+// sibling's keep bits with the same philox4(seed_g, flat/8) counter /
+// 16-bit lanes / threshold as dropout_mask_kernel, writes the mask byte, and
+// forms the dropped operand with the same bf16 rounding
+// (from_f32(to_f32(x) * inv_keep)) — every philox value is computed by
+// exactly one lane, and the masks are bit-identical to dropout_mask_fwd.
+//
+// The A_g k-slices (the MFMA B operand, shared by the four waves) are
+// staged in LDS as [G*r][32] row-major, double buffered, one barrier per
+// k-tile; the next tile's global loads are issued before the MFMA work of
+// the current one, and x is prefetched several tiles ahead in registers.  Rows are 64 B = one fragment row, so staging writes
+// (thread t -> bytes 16t..16t+15) and fragment reads (lane (n,kg) -> byte
+// n*64 + kg*16) both cover one contiguous 1 KiB per wave instruction:
+// conflict-free without padding or rotation.
+//
+// RMAX (128 or 256) bounds the static accumulator array; fragments past the
+// runtime r are skipped by wave-uniform branches.  DROP=false (p == 0 or
+// eval) skips the philox and writes no mask.
+// ---------------------------------------------------------------------------
+
+struct LoraDownArgs {
+  const __hip_bfloat16* A[3];
+  __hip_bfloat16* t[3];
+  uint8_t* mask[3];
+  uint64_t seed[3];
+};
+
+template <int G, int RMAX, bool DROP>
+__global__ __launch_bounds__(256) void lora_down_dropout_kernel(
+    const __hip_bfloat16* __restrict__ x, LoraDownArgs a, long M, int K, int r,
+    float p, float inv_keep) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int BK = 32;
+  constexpr int NF = RMAX / 16;             // column fragments per sibling
+  const int ncols = G * r;                  // LDS tile rows in use
+  __bf16* bt = (__bf16*)smem;               // [2][ncols][BK]
+
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int fr = lane & 15;
+  const int kg = (lane >> 4) * 8;
+  const long row = (long)blockIdx.x * 64 + wave * 16 + fr;
+  const bool row_ok = row < M;
+  const uint32_t thr = (uint32_t)(p * 65536.0f);
+
+  f32x4 acc[G][NF];
+#pragma unroll
+  for (int g = 0; g < G; ++g)
+#pragma unroll
+    for (int j = 0; j < NF; ++j) acc[g][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  // staging slots: for sibling g (static) and i < RMAX/64, this thread owns
+  // tile row n = tid/4 + 64*i of A_g (while n < r) and k = (tid%4)*8
+  constexpr int NSL = RMAX / 64;
+  bf16x8 gb[G][NSL];
+  const int sn = threadIdx.x >> 2;
+  const int sk = (threadIdx.x & 3) * 8;
+  auto load_b = [&](int k0) {
+#pragma unroll
+    for (int g = 0; g < G; ++g)
+#pragma unroll
+      for (int i = 0; i < NSL; ++i) {
+        const int n = sn + i * 64;
+        gb[g][i] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+        if (n < r && k0 + sk + 8 <= K)
+          gb[g][i] = *reinterpret_cast<const bf16x8*>(a.A[g] + (long)n * K + k0 + sk);
+      }
+  };
+  auto store_b = [&](int buf) {
+    __bf16* dst = bt + (long)buf * ncols * BK;
+#pragma unroll
+    for (int g = 0; g < G; ++g)
+#pragma unroll
+      for (int i = 0; i < NSL; ++i) {
+        const int n = sn + i * 64;
+        if (n < r)
+          *reinterpret_cast<bf16x8*>(dst + (g * r + n) * BK + sk) = gb[g][i];
+      }
+  };
+  auto load_x = [&](int k0) {
+    Vec8<__hip_bfloat16> v;
+    if (row_ok && k0 + kg + 8 <= K) {
+      v = load8(x + row * (long)K + k0 + kg);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v.v[j] = from_f32<__hip_bfloat16>(0.f);
+    }
+    return v;
+  };
+
+  // x runs XPF k-tiles ahead in a register ring: with one wave per SIMD the
+  // HBM latency of a single 64-byte-per-row tile is not covered by one
+  // tile's work, XPF tiles in flight are
+  constexpr int XPF = 4;
+  Vec8<__hip_bfloat16> xq[XPF];
+  load_b(0);
+#pragma unroll
+  for (int s = 0; s < XPF; ++s) xq[s] = load_x(s * BK);
+  store_b(0);
+  __syncthreads();
+
+  const int ntiles = (K + BK - 1) / BK;
+  for (int kt0 = 0; kt0 < ntiles; kt0 += XPF) {
+#pragma unroll
+    for (int s = 0; s < XPF; ++s) {
+      const int kt = kt0 + s;
+      if (kt >= ntiles) break;  // block-uniform
+      const int k0 = kt * BK;
+      const int buf = kt & 1;
+      const bool more = kt + 1 < ntiles;
+      const Vec8<__hip_bfloat16> xc = xq[s];
+      if (more) load_b(k0 + BK);
+      xq[s] = load_x(k0 + XPF * BK);  // zeros, no load, past K
+      const bool grp_ok = row_ok && k0 + kg + 8 <= K;  // this lane's 8 elements exist
+      const __bf16* bsrc = bt + (long)buf * ncols * BK;
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        union { Vec8<__hip_bfloat16> h; bf16x8 v; } op;
+        if (DROP) {
+          const long i8 = (row * (long)K + k0 + kg) >> 3;
+          uint32_t rr[4];
+          philox4(a.seed[g], (uint64_t)i8, rr);
+          const uint32_t u16s[8] = {rr[0] & 0xFFFFu, rr[0] >> 16, rr[1] & 0xFFFFu,
+                                    rr[1] >> 16, rr[2] & 0xFFFFu, rr[2] >> 16,
+                                    rr[3] & 0xFFFFu, rr[3] >> 16};
+          uint8_t m = 0;
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            const bool keep = u16s[j] >= thr;
+            m |= (uint8_t)keep << j;
+            op.h.v[j] = keep ? from_f32<__hip_bfloat16>(to_f32(xc.v[j]) * inv_keep)
+                             : from_f32<__hip_bfloat16>(0.f);
+          }
+          if (grp_ok) a.mask[g][i8] = m;
+        } else {
+          op.h = xc;
+        }
+#pragma unroll
+        for (int j = 0; j < NF; ++j) {
+          if (j * 16 < r) {
+            const bf16x8 b = *reinterpret_cast<const bf16x8*>(
+                bsrc + (g * r + j * 16 + fr) * BK + kg);
+            acc[g][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(op.v, b, acc[g][j], 0, 0, 0);
+          }
+        }
+      }
+      if (more) store_b(buf ^ 1);
+      __syncthreads();
+    }
+  }
+
+  // epilogue: C fragment rows crow..crow+3 of this wave's 16, column fr
+  const long orow0 = (long)blockIdx.x * 64 + wave * 16 + (lane >> 4) * 4;
+#pragma unroll
+  for (int g = 0; g < G; ++g)
+#pragma unroll
+    for (int j = 0; j < NF; ++j) {
+      if (j * 16 < r) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          if (orow0 + q < M)
+            a.t[g][(orow0 + q) * (long)r + j * 16 + fr] =
+                from_f32<__hip_bfloat16>(acc[g][j][q]);
+      }
+    }
+}
+
+template <int G, int RMAX>
+static void launch_lora_down(bool drop, dim3 grid, size_t lds, hipStream_t stream,
+                             const __hip_bfloat16* x, const LoraDownArgs& a,
+                             long M, int K, int r, float p, float inv_keep) {
+  if (drop)
+    hipLaunchKernelGGL((lora_down_dropout_kernel<G, RMAX, true>), grid, dim3(256), lds,
+                       stream, x, a, M, K, r, p, inv_keep);
+  else
+    hipLaunchKernelGGL((lora_down_dropout_kernel<G, RMAX, false>), grid, dim3(256), lds,
+                       stream, x, a, M, K, r, 0.f, 1.f);
+}
+
+// x[M,K], As = G x [r,K], seeds = G philox seeds -> {t_0..t_{G-1}} followed,
+// when p > 0, by {mask_0..mask_{G-1}} (FLAT-packed, as dropout_mask_fwd).
+// p == 0: no masks, seeds ignored.
+std::vector<torch::Tensor> lora_down_dropout(torch::Tensor x, std::vector<torch::Tensor> As,
+                                             std::vector<int64_t> seeds, double p) {
+  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 2);
+  TORCH_CHECK(x.scalar_type() == torch::kBFloat16, "lora_down_dropout: bf16 only");
+  const int G = (int)As.size();
+  TORCH_CHECK(G >= 1 && G <= 3, "lora_down_dropout: 1..3 siblings");
+  const bool drop = p > 0.0;
+  TORCH_CHECK(p >= 0.0 && p < 1.0, "lora_down_dropout: p in [0,1)");
+  TORCH_CHECK(!drop || (int)seeds.size() == G, "lora_down_dropout: one seed per sibling");
+  TORCH_CHECK(As[0].dim() == 2, "lora_down_dropout: A_g must be contiguous bf16 [r,K]");
+  const long M = x.size(0);
+  const int K = x.size(1);
+  const int r = As[0].size(0);
+  TORCH_CHECK(M >= 1 && K % 8 == 0, "lora_down_dropout: K must be a multiple of 8");
+  TORCH_CHECK(r % 32 == 0 && r <= 256, "lora_down_dropout: r must be a multiple of 32, <=256");
+  LoraDownArgs a = {};
+  std::vector<torch::Tensor> out;
+  for (int g = 0; g < G; ++g) {
+    TORCH_CHECK(As[g].is_cuda() && As[g].is_contiguous() &&
+                As[g].scalar_type() == torch::kBFloat16 && As[g].dim() == 2 &&
+                As[g].size(0) == r && As[g].size(1) == K,
+                "lora_down_dropout: A_g must be contiguous bf16 [r,K]");
+    out.push_back(torch::empty({M, (long)r}, x.options()));
+    a.A[g] = (const __hip_bfloat16*)As[g].data_ptr();
+    a.t[g] = (__hip_bfloat16*)out[g].data_ptr();
+  }
+  if (drop) {
+    const long n8 = (M * (long)K + 7) / 8;
+    for (int g = 0; g < G; ++g) {
+      out.push_back(torch::empty({n8}, x.options().dtype(torch::kUInt8)));
+      a.mask[g] = out[G + g].data_ptr<uint8_t>();
+      a.seed[g] = (uint64_t)seeds[g];
+    }
+  }
+  auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
+  const size_t lds = 2u * (size_t)G * r * 32 * sizeof(__bf16);
+  dim3 grid((unsigned)((M + 63) / 64));
+  const __hip_bfloat16* xp = (const __hip_bfloat16*)x.data_ptr();
+  const float pf = (float)p;
+  const float inv_keep = 1.f / (1.f - pf);
+#define LORA_DOWN_CASE(GG)                                                        \
+  case GG:                                                                        \
+    if (r <= 128) launch_lora_down<GG, 128>(drop, grid, lds, stream, xp, a, M, K, \
+                                            r, pf, inv_keep);                     \
+    else launch_lora_down<GG, 256>(drop, grid, lds, stream, xp, a, M, K, r, pf,   \
+                                   inv_keep);                                     \
+    break;
+  switch (G) {
+    LORA_DOWN_CASE(1)
+    LORA_DOWN_CASE(2)
+    LORA_DOWN_CASE(3)
+  }
+#undef LORA_DOWN_CASE
+  HIP_CHECK_LAST();
+  return out;
 }

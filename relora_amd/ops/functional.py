@@ -716,3 +716,111 @@ def lora_linear(x, weight, bias, lora_A, lora_B, scale, dropout_p=0.0,
     if lora_only:
         return lora_out * scale
     return F.linear(x, weight, bias) + lora_out * scale
+
+
+# ---------------------------------------------------------------------------
+# Group LoRA linear: G <= 3 sibling projections that share one input
+# (q/k/v, gate/up).  One lora_down_dropout launch reads x once for every
+# sibling's dropout + rank-r down-projection, and backward accumulates all
+# siblings' input gradients into one dx buffer (ops/csrc/lora_group.cpp).
+# RELORA_AMD_LORA_GROUP=0 disables grouping (read at import, for A/B runs).
+# ---------------------------------------------------------------------------
+
+_LORA_GROUP = os.environ.get("RELORA_AMD_LORA_GROUP", "1") != "0"
+
+
+class _LoRALinearGroup(torch.autograd.Function):
+    """`tensors` is (weight, bias-or-None, lora_A, lora_B) per sibling,
+    flattened; returns one output per sibling."""
+
+    @staticmethod
+    def forward(ctx, x, scales, dropout_p, training, *tensors):
+        G = len(scales)
+        Ws, biases = tensors[0::4], tensors[1::4]
+        As, Bs = tensors[2::4], tensors[3::4]
+        in_shape = x.shape
+        K = in_shape[-1]
+        x2d = x.contiguous().view(-1, K)
+        use_dropout = dropout_p > 0 and training
+        # one seed per sibling, in sibling order: the philox stream position
+        # and every mask equal what sequential per-module calls produce
+        seeds = ([_next_dropout_seed() & 0x7FFFFFFFFFFFFFFF for _ in range(G)]
+                 if use_dropout else [])
+        empty = x2d.new_empty(0)
+        fused = [int(_use_fused_k1(x2d, W, A)) for W, A in zip(Ws, As)]
+        out = hip.ext().lora_group_fwd(
+            x2d, list(Ws), [b if b is not None else empty for b in biases],
+            [A.contiguous() for A in As], [B.contiguous() for B in Bs],
+            [float(s) for s in scales],
+            seeds, dropout_p if use_dropout else 0.0, fused)
+        ys, ts, bss = out[:G], out[G:2 * G], out[2 * G:3 * G]
+        masks = out[3 * G:]
+        ctx.save_for_backward(x2d, *ts, *bss, *masks, *Ws, *As)
+        ctx.G = G
+        ctx.scales = [float(s) for s in scales]
+        ctx.dropout_p = dropout_p if use_dropout else 0.0
+        ctx.has_bias = [b is not None for b in biases]
+        return tuple(y.view(*in_shape[:-1], y.shape[-1]) for y in ys)
+
+    @staticmethod
+    def backward(ctx, *dys):
+        G, p = ctx.G, ctx.dropout_p
+        saved = ctx.saved_tensors
+        x2d = saved[0]
+        ts, bss = saved[1:1 + G], saved[1 + G:1 + 2 * G]
+        nm = G if p > 0 else 0
+        masks = saved[1 + 2 * G:1 + 2 * G + nm]
+        Ws = saved[1 + 2 * G + nm:1 + 3 * G + nm]
+        As = saved[1 + 3 * G + nm:1 + 4 * G + nm]
+        dy2d = [dy.contiguous().view(-1, W.shape[0]) for dy, W in zip(dys, Ws)]
+        out = hip.ext().lora_group_bwd(
+            dy2d, x2d, list(masks), list(ts), list(Ws),
+            [A.contiguous() for A in As], list(bss), ctx.scales, p)
+        dx, dAs, dBs = out[0], out[1:1 + G], out[1 + G:1 + 2 * G]
+        grads = []
+        for g in range(G):
+            # needs_input_grad index: 4 leading non-sibling args, 4 per sibling
+            dw = dy2d[g].t() @ x2d if ctx.needs_input_grad[4 + 4 * g] else None
+            dbias = (dy2d[g].sum(0)
+                     if ctx.has_bias[g] and ctx.needs_input_grad[5 + 4 * g] else None)
+            grads += [dw, dbias, dAs[g], dBs[g]]
+        return (dx.view(dys[0].shape[:-1] + (x2d.shape[1],)), None, None, None,
+                *grads)
+
+
+def lora_group_ok(x, specs):
+    """Shapes and dtypes the group op takes: bf16 on the HIP path, K % 8 == 0,
+    one shared r with r % 32 == 0 and r <= 128, float scales, 1..3 siblings.
+    The kernels take r <= 256, but at r = 256 lora_down_dropout measured
+    slower than the launches it replaces (174 vs 101 us at G=2, 247 vs 152 us
+    at G=3) and llama_7b did not gain, so r > 128 keeps the per-linear path
+    (profiles/stage6_lora_group.md)."""
+    if not (_LORA_GROUP and 1 <= len(specs) <= 3):
+        return False
+    if x.dtype != torch.bfloat16 or not hip.use_hip(x, "lora"):
+        return False
+    if os.environ.get("RELORA_AMD_LORA_PATH", "fused") == "torch":
+        return False
+    K = x.shape[-1]
+    r = specs[0][2].shape[0]
+    if K % 8 != 0 or r % 32 != 0 or r > 128:
+        return False
+    for weight, bias, lora_A, lora_B, scale in specs:
+        if weight is None or torch.is_tensor(scale):
+            return False
+        if weight.dtype != torch.bfloat16 or lora_A.dtype != torch.bfloat16:
+            return False
+        if lora_A.shape != (r, K) or weight.shape[1] != K:
+            return False
+    return True
+
+
+def lora_linear_group(x, specs, dropout_p=0.0, training=False):
+    """[lora_linear(x, *spec) for spec in specs] for siblings that share the
+    input `x`, as one group op.  `specs` is a list of (weight, bias, lora_A,
+    lora_B, scale); callers check `lora_group_ok` first."""
+    flat = []
+    for weight, bias, lora_A, lora_B, _ in specs:
+        flat += [weight, bias, lora_A, lora_B]
+    return list(_LoRALinearGroup.apply(
+        x, tuple(float(s[4]) for s in specs), dropout_p, training, *flat))

@@ -330,3 +330,30 @@ class ReLoRaLinear(nn.Module):
     def extra_repr(self):
         return (f"in_features={self.in_features}, out_features={self.out_features}, "
                 f"r={self.r}, lora_alpha={self.lora_alpha}")
+
+
+def lora_group_forward(x, modules):
+    """[m(x) for m in modules] for sibling projections that share the input
+    `x` (q/k/v, gate/up).  When every module is a plain (not quantized, not
+    lora_only, float-scale) ReLoRaLinear with the same r and dropout p and
+    the shapes suit the kernels (r <= 128), the siblings run as one group op
+    (`ops.lora_linear_group`): one dropout + down-projection pass over x for
+    all of them and one shared input-gradient buffer in backward.  Anything
+    else — CPU, fp32, hooks registered on a module, RELORA_AMD_LORA_GROUP=0 —
+    calls the modules one by one, exactly as before."""
+    modules = list(modules)
+    first = modules[0]
+    groupable = x.is_cuda and all(
+        isinstance(m, ReLoRaLinear) and m.quantize is None and not m.lora_only
+        and not m.trainable_scaling and m.r == first.r
+        and m.lora_dropout_p == first.lora_dropout_p
+        and m.training == first.training
+        and not m._forward_hooks and not m._forward_pre_hooks
+        for m in modules)
+    if groupable:
+        specs = [(m.weight, m.bias, m.lora_A.weight, m.lora_B.weight,
+                  m._post_lora_scale()) for m in modules]
+        if ops.lora_group_ok(x, specs):
+            return ops.lora_linear_group(x, specs, dropout_p=first.lora_dropout_p,
+                                         training=first.training)
+    return [m(x) for m in modules]
