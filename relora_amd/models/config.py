@@ -23,6 +23,7 @@ class LlamaConfig(PretrainedConfig):
         intermediate_size=11008,
         num_hidden_layers=32,
         num_attention_heads=32,
+        num_key_value_heads=None,
         hidden_act="silu",
         max_position_embeddings=2048,
         initializer_range=0.02,
@@ -40,6 +41,15 @@ class LlamaConfig(PretrainedConfig):
         self.intermediate_size = intermediate_size
         self.num_hidden_layers = num_hidden_layers
         self.num_attention_heads = num_attention_heads
+        # grouped-query attention (same field as HF's LlamaConfig): None means
+        # one kv head per query head, i.e. plain multi-head attention
+        if num_key_value_heads is None:
+            num_key_value_heads = num_attention_heads
+        if num_key_value_heads < 1 or num_attention_heads % num_key_value_heads != 0:
+            raise ValueError(
+                f"num_key_value_heads ({num_key_value_heads}) must divide "
+                f"num_attention_heads ({num_attention_heads})")
+        self.num_key_value_heads = num_key_value_heads
         self.hidden_act = hidden_act
         # the reference config JSONs carry `max_sequence_length`; the reference
         # model consumes `max_position_embeddings` (default 2048) for the RoPE
@@ -56,6 +66,15 @@ class LlamaConfig(PretrainedConfig):
             tie_word_embeddings=tie_word_embeddings,
             **kwargs,
         )
+
+    def to_dict(self):
+        # `num_key_value_heads` goes to JSON under HF's name, but only when it
+        # says something: a multi-head config is written exactly as before
+        # (HF and this class both default the field to num_attention_heads)
+        d = super().to_dict()
+        if d.get("num_key_value_heads") == d.get("num_attention_heads"):
+            d.pop("num_key_value_heads", None)
+        return d
 
 
 class GPTNeoXConfig(PretrainedConfig):

@@ -100,9 +100,15 @@ class LlamaAttention(nn.Module):
         self.head_dim = self.hidden_size // self.num_heads
         if self.head_dim * self.num_heads != self.hidden_size:
             raise ValueError("hidden_size must be divisible by num_attention_heads")
+        # grouped-query attention: query head h reads kv head h // n_rep
+        # (HF repeat_kv convention); nkv == num_heads is plain multi-head
+        self.num_key_value_heads = getattr(config, "num_key_value_heads", None) or self.num_heads
+        if self.num_heads % self.num_key_value_heads != 0:
+            raise ValueError("num_attention_heads must be divisible by num_key_value_heads")
+        kv_size = self.num_key_value_heads * self.head_dim
         self.q_proj = nn.Linear(self.hidden_size, self.hidden_size, bias=False)
-        self.k_proj = nn.Linear(self.hidden_size, self.hidden_size, bias=False)
-        self.v_proj = nn.Linear(self.hidden_size, self.hidden_size, bias=False)
+        self.k_proj = nn.Linear(self.hidden_size, kv_size, bias=False)
+        self.v_proj = nn.Linear(self.hidden_size, kv_size, bias=False)
         self.o_proj = nn.Linear(self.hidden_size, self.hidden_size, bias=False)
         self.rotary_emb = LlamaRotaryEmbedding(
             self.head_dim, max_position_embeddings=config.max_position_embeddings,
@@ -119,8 +125,8 @@ class LlamaAttention(nn.Module):
         bsz, q_len, _ = hidden_states.size()
         q, k, v = lora_group_forward(hidden_states, (self.q_proj, self.k_proj, self.v_proj))
         q = q.view(bsz, q_len, self.num_heads, self.head_dim).transpose(1, 2)
-        k = k.view(bsz, q_len, self.num_heads, self.head_dim).transpose(1, 2)
-        v = v.view(bsz, q_len, self.num_heads, self.head_dim).transpose(1, 2)
+        k = k.view(bsz, q_len, self.num_key_value_heads, self.head_dim).transpose(1, 2)
+        v = v.view(bsz, q_len, self.num_key_value_heads, self.head_dim).transpose(1, 2)
 
         kv_seq_len = q_len
         if past_key_value is not None:
@@ -135,7 +141,7 @@ class LlamaAttention(nn.Module):
         if past_key_value is not None:
             k = torch.cat([past_key_value[0], k], dim=2)
             v = torch.cat([past_key_value[1], v], dim=2)
-        present = (k, v) if use_cache else None
+        present = (k, v) if use_cache else None  # nkv heads: never expanded
 
         # parity with the reference: attention is ALWAYS causal in training;
         # padding masks are ignored (reference modeling_llama.py:221-224).

@@ -249,12 +249,12 @@ DEV_INLINE void tile_write_t(__bf16* dst, const bf16x8 (&r)[NV]) {
 // forward
 // ---------------------------------------------------------------------------
 
-template <int HD>  // padded head dim (multiple of 32), actual hd passed in
+template <int HD, bool GQA = false>  // padded head dim (multiple of 32), actual hd passed in
 __global__ __launch_bounds__(512) void attn_fwd_kernel(
     const __hip_bfloat16* __restrict__ q, const __hip_bfloat16* __restrict__ k,
     const __hip_bfloat16* __restrict__ v, __hip_bfloat16* __restrict__ out,
     float* __restrict__ lse, int S, int hd, int nh, long bst, long hst, int ld,
-    float scale) {
+    long bst_kv, long hst_kv, int ld_kv, int n_rep, float scale) {
   constexpr int KFRAGS = HD / 32;      // QK^T k-steps
   constexpr int NT_HD = HD / 16;       // PV hd tiles
   constexpr int LDK = HD + LPAD;
@@ -276,9 +276,13 @@ __global__ __launch_bounds__(512) void attn_fwd_kernel(
   // so the causal work imbalance doesn't leave a long tail
   const int q_start = (gridDim.x - 1 - blockIdx.x) * (128 * RF);
   const long base = (long)(bh / nh) * bst + (long)(bh % nh) * hst;
+  // query head h reads kv head h / n_rep through the kv stride triple
+  const long base_kv = GQA ? (long)(bh / nh) * bst_kv + (long)((bh % nh) / n_rep) * hst_kv
+                           : base;
+  const int ldk = GQA ? ld_kv : ld;
   const __hip_bfloat16* qp = q + base;
-  const __hip_bfloat16* kp = k + base;
-  const __hip_bfloat16* vp = v + base;
+  const __hip_bfloat16* kp = k + base_kv;
+  const __hip_bfloat16* vp = v + base_kv;
 
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -313,13 +317,13 @@ __global__ __launch_bounds__(512) void attn_fwd_kernel(
   const int n_tiles = (q_max_abs / TILE) + 1;  // causal bound
 
   bf16x8 rk[NV], rv[NV];
-  tile_load_regs<HD, NV>(rk, kp, 0, S, hd, ld);
-  tile_load_regs<HD, NV>(rv, vp, 0, S, hd, ld);
+  tile_load_regs<HD, NV>(rk, kp, 0, S, hd, ldk);
+  tile_load_regs<HD, NV>(rv, vp, 0, S, hd, ldk);
   tile_write_rows<HD, NV>(lds_k, rk, LDK);
   tile_write_t<HD, NV>(lds_vt, rv);
   if (n_tiles > 1) {
-    tile_load_regs<HD, NV>(rk, kp, TILE, S, hd, ld);
-    tile_load_regs<HD, NV>(rv, vp, TILE, S, hd, ld);
+    tile_load_regs<HD, NV>(rk, kp, TILE, S, hd, ldk);
+    tile_load_regs<HD, NV>(rv, vp, TILE, S, hd, ldk);
   }
   __syncthreads();
 
@@ -370,8 +374,8 @@ __global__ __launch_bounds__(512) void attn_fwd_kernel(
         tile_write_rows<HD, NV>(lds_k + (cur ^ 1) * TILE * LDK, rk, LDK);
         tile_write_t<HD, NV>(lds_vt + (cur ^ 1) * HD * TILE, rv);
         if (kt + 2 < n_tiles) {
-          tile_load_regs<HD, NV>(rk, kp, (kt + 2) * TILE, S, hd, ld);
-          tile_load_regs<HD, NV>(rv, vp, (kt + 2) * TILE, S, hd, ld);
+          tile_load_regs<HD, NV>(rk, kp, (kt + 2) * TILE, S, hd, ldk);
+          tile_load_regs<HD, NV>(rv, vp, (kt + 2) * TILE, S, hd, ldk);
         }
       }
 
@@ -502,12 +506,12 @@ DEV_INLINE bf16x8 pack_p_frag(const float* p16, int g) {
 #define LOG2E 1.44269504088896340736f
 #define DEFER_MAX_THR 11.5f  // log2 domain ~ e^8 (guide T13; bf16 accum headroom)
 
-template <int HD, int MINW = 2, bool TRR = false>
+template <int HD, int MINW = 2, bool TRR = false, bool GQA = false>
 __global__ __launch_bounds__(512, MINW) void attn_fwd_v3_kernel(
     const __hip_bfloat16* __restrict__ q, const __hip_bfloat16* __restrict__ k,
     const __hip_bfloat16* __restrict__ v, __hip_bfloat16* __restrict__ out,
     float* __restrict__ lse, int S, int hd, int nh, long bst, long hst, int ld,
-    float scale) {
+    long bst_kv, long hst_kv, int ld_kv, int n_rep, float scale) {
   constexpr int KSTEPS = HD / 16;  // QK^T k-steps per 32-kv subtile
   constexpr int NT32 = HD / 32;    // O^T 32-row hd tiles
   constexpr int LDK = HD + LPAD;
@@ -520,9 +524,13 @@ __global__ __launch_bounds__(512, MINW) void attn_fwd_v3_kernel(
   const int bh = blockIdx.y;
   const int q_start = (gridDim.x - 1 - blockIdx.x) * 256;  // heavy blocks first
   const long base = (long)(bh / nh) * bst + (long)(bh % nh) * hst;
+  // query head h reads kv head h / n_rep through the kv stride triple
+  const long base_kv = GQA ? (long)(bh / nh) * bst_kv + (long)((bh % nh) / n_rep) * hst_kv
+                           : base;
+  const int ldk = GQA ? ld_kv : ld;
   const __hip_bfloat16* qp = q + base;
-  const __hip_bfloat16* kp = k + base;
-  const __hip_bfloat16* vp = v + base;
+  const __hip_bfloat16* kp = k + base_kv;
+  const __hip_bfloat16* vp = v + base_kv;
 
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -547,14 +555,14 @@ __global__ __launch_bounds__(512, MINW) void attn_fwd_v3_kernel(
   const float sc2 = scale * LOG2E;
 
   bf16x8 rk[NV], rv[NV];
-  tile_load_regs<HD, NV>(rk, kp, 0, S, hd, ld);
-  tile_load_regs<HD, NV>(rv, vp, 0, S, hd, ld);
+  tile_load_regs<HD, NV>(rk, kp, 0, S, hd, ldk);
+  tile_load_regs<HD, NV>(rv, vp, 0, S, hd, ldk);
   if (TRR) tile_write_tr<HD, NV>(lds_vt, rv);
   else tile_write_t<HD, NV>(lds_vt, rv);
   tile_write_rows<HD, NV>(lds_k, rk, LDK);
   if (n_tiles > 1) {
-    tile_load_regs<HD, NV>(rk, kp, TILE, S, hd, ld);
-    tile_load_regs<HD, NV>(rv, vp, TILE, S, hd, ld);
+    tile_load_regs<HD, NV>(rk, kp, TILE, S, hd, ldk);
+    tile_load_regs<HD, NV>(rv, vp, TILE, S, hd, ldk);
   }
   __syncthreads();
 
@@ -601,8 +609,8 @@ __global__ __launch_bounds__(512, MINW) void attn_fwd_v3_kernel(
         if (TRR) tile_write_tr<HD, NV>(lds_vt + (cur ^ 1) * HD * TILE, rv);
         else tile_write_t<HD, NV>(lds_vt + (cur ^ 1) * HD * TILE, rv);
         if (kt + 2 < n_tiles) {
-          tile_load_regs<HD, NV>(rk, kp, (kt + 2) * TILE, S, hd, ld);
-          tile_load_regs<HD, NV>(rv, vp, (kt + 2) * TILE, S, hd, ld);
+          tile_load_regs<HD, NV>(rk, kp, (kt + 2) * TILE, S, hd, ldk);
+          tile_load_regs<HD, NV>(rv, vp, (kt + 2) * TILE, S, hd, ldk);
         }
       }
 
@@ -739,14 +747,14 @@ DEV_INLINE f32x4 load_f32x4_guard(const float* p, long idx, long n) {
   return r;
 }
 
-template <int HD, int NWAVE = 8, int MINW = 2>  // NWAVE*32 q rows per block;
-                                  // MINW=4 caps VGPRs at 128 (occ experiment)
+template <int HD, int NWAVE = 8, int MINW = 2, bool GQA = false>
+// NWAVE*32 q rows per block; MINW=4 caps VGPRs at 128 (occ experiment)
 __global__ __launch_bounds__(NWAVE * 64, MINW) void attn_bwd_dq_v3_kernel(
     const __hip_bfloat16* __restrict__ q, const __hip_bfloat16* __restrict__ k,
     const __hip_bfloat16* __restrict__ v, const __hip_bfloat16* __restrict__ dout,
     const float* __restrict__ lse, const float* __restrict__ delta,
     __hip_bfloat16* __restrict__ dq, int S, int hd, int nh, long bst, long hst,
-    int ld, float scale) {
+    int ld, long bst_kv, long hst_kv, int ld_kv, int n_rep, float scale) {
   constexpr int KSTEPS = HD / 16;
   constexpr int NT32 = HD / 32;
   constexpr int LDK = HD + LPAD;
@@ -762,9 +770,13 @@ __global__ __launch_bounds__(NWAVE * 64, MINW) void attn_bwd_dq_v3_kernel(
   const int bh = blockIdx.y;
   const int q_start = (gridDim.x - 1 - blockIdx.x) * QROWS;  // heavy blocks first
   const long base = (long)(bh / nh) * bst + (long)(bh % nh) * hst;
+  // query head h reads kv head h / n_rep through the kv stride triple
+  const long base_kv = GQA ? (long)(bh / nh) * bst_kv + (long)((bh % nh) / n_rep) * hst_kv
+                           : base;
+  const int ldk = GQA ? ld_kv : ld;
   const __hip_bfloat16* qp = q + base;
-  const __hip_bfloat16* kp = k + base;
-  const __hip_bfloat16* vp = v + base;
+  const __hip_bfloat16* kp = k + base_kv;
+  const __hip_bfloat16* vp = v + base_kv;
   const __hip_bfloat16* dop = dout + base;
 
   const int lane = threadIdx.x & 63;
@@ -791,14 +803,14 @@ __global__ __launch_bounds__(NWAVE * 64, MINW) void attn_bwd_dq_v3_kernel(
   const int n_tiles = (q_max_abs / TILE) + 1;
 
   bf16x8 rk[NV], rv[NV];
-  tile_load_regs<HD, NV, NT>(rk, kp, 0, S, hd, ld);
-  tile_load_regs<HD, NV, NT>(rv, vp, 0, S, hd, ld);
+  tile_load_regs<HD, NV, NT>(rk, kp, 0, S, hd, ldk);
+  tile_load_regs<HD, NV, NT>(rv, vp, 0, S, hd, ldk);
   tile_write_rows<HD, NV, NT>(lds_k, rk, LDK);
   tile_write_rows<HD, NV, NT>(lds_v, rv, LDK);
   tile_write_t<HD, NV, NT>(lds_kt, rk);
   if (n_tiles > 1) {
-    tile_load_regs<HD, NV, NT>(rk, kp, TILE, S, hd, ld);
-    tile_load_regs<HD, NV, NT>(rv, vp, TILE, S, hd, ld);
+    tile_load_regs<HD, NV, NT>(rk, kp, TILE, S, hd, ldk);
+    tile_load_regs<HD, NV, NT>(rv, vp, TILE, S, hd, ldk);
   }
   __syncthreads();
 
@@ -848,8 +860,8 @@ __global__ __launch_bounds__(NWAVE * 64, MINW) void attn_bwd_dq_v3_kernel(
         tile_write_rows<HD, NV, NT>(lds_v + (cur ^ 1) * TILE * LDK, rv, LDK);
         tile_write_t<HD, NV, NT>(lds_kt + (cur ^ 1) * HD * TILE, rk);
         if (kt + 2 < n_tiles) {
-          tile_load_regs<HD, NV, NT>(rk, kp, (kt + 2) * TILE, S, hd, ld);
-          tile_load_regs<HD, NV, NT>(rv, vp, (kt + 2) * TILE, S, hd, ld);
+          tile_load_regs<HD, NV, NT>(rk, kp, (kt + 2) * TILE, S, hd, ldk);
+          tile_load_regs<HD, NV, NT>(rv, vp, (kt + 2) * TILE, S, hd, ldk);
         }
       }
 
@@ -884,13 +896,15 @@ __global__ __launch_bounds__(NWAVE * 64, MINW) void attn_bwd_dq_v3_kernel(
   }
 }
 
-template <int HD, bool TRR = false>  // HD <= 64; TRR: tr-read Q^T/dO^T images
+template <int HD, bool TRR = false, bool GQA = false>
+// HD <= 64; TRR: tr-read Q^T/dO^T images
 __global__ __launch_bounds__(512) void attn_bwd_dkdv_v3_kernel(
     const __hip_bfloat16* __restrict__ q, const __hip_bfloat16* __restrict__ k,
     const __hip_bfloat16* __restrict__ v, const __hip_bfloat16* __restrict__ dout,
     const float* __restrict__ lse, const float* __restrict__ delta,
     __hip_bfloat16* __restrict__ dk, __hip_bfloat16* __restrict__ dv,
-    int S, int hd, int nh, long bst, long hst, int ld, float scale) {
+    int S, int hd, int nh, long bst, long hst, int ld, long bst_kv, long hst_kv,
+    int ld_kv, int n_rep, float scale) {
   constexpr int KSTEPS = HD / 16;
   constexpr int NT32 = HD / 32;
   constexpr int LDK = HD + LPAD;
@@ -904,13 +918,18 @@ __global__ __launch_bounds__(512) void attn_bwd_dkdv_v3_kernel(
 
   const int bh = blockIdx.y;
   const int kv_start = blockIdx.x * 256;
-  const long base = (long)(bh / nh) * bst + (long)(bh % nh) * hst;
-  const __hip_bfloat16* qp = q + base;
-  const __hip_bfloat16* kp = k + base;
-  const __hip_bfloat16* vp = v + base;
-  const __hip_bfloat16* dop = dout + base;
-  const float* lsep = lse + (long)bh * S;
-  const float* deltap = delta + (long)bh * S;
+  // MHA: blockIdx.y = (b, head) and one base serves everything.  GQA:
+  // blockIdx.y = (b, kv head); the block owns its kv rows and loops over the
+  // n_rep query heads of its group, accumulating into the same dk/dv
+  // registers — no atomics, no per-head planes, one fp32 sum per group.
+  const int nkv = GQA ? nh / n_rep : nh;
+  const int bi = bh / nkv;
+  const int hk = bh % nkv;
+  const long base_kv = GQA ? (long)bi * bst_kv + (long)hk * hst_kv
+                           : (long)(bh / nh) * bst + (long)(bh % nh) * hst;
+  const int ldk = GQA ? ld_kv : ld;
+  const __hip_bfloat16* kp = k + base_kv;
+  const __hip_bfloat16* vp = v + base_kv;
 
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -921,8 +940,8 @@ __global__ __launch_bounds__(512) void attn_bwd_dkdv_v3_kernel(
   bf16x8 kf[KSTEPS], vf[KSTEPS];
 #pragma unroll
   for (int ks = 0; ks < KSTEPS; ++ks) {
-    kf[ks] = global_frag(kp, kv_abs, S, hd, ld, ks * 16 + hi * 8);
-    vf[ks] = global_frag(vp, kv_abs, S, hd, ld, ks * 16 + hi * 8);
+    kf[ks] = global_frag(kp, kv_abs, S, hd, ldk, ks * 16 + hi * 8);
+    vf[ks] = global_frag(vp, kv_abs, S, hd, ldk, ks * 16 + hi * 8);
   }
   const float sc2 = scale * LOG2E;
 
@@ -937,110 +956,125 @@ __global__ __launch_bounds__(512) void attn_bwd_dkdv_v3_kernel(
   const int n_q_tiles = (S + TILE - 1) / TILE;
 
   bf16x8 rq[NV], rdo[NV];
-  tile_load_regs<HD, NV>(rq, qp, first_qt * TILE, S, hd, ld);
-  tile_load_regs<HD, NV>(rdo, dop, first_qt * TILE, S, hd, ld);
-  tile_write_rows<HD, NV>(lds_q, rq, LDK);
-  tile_write_rows<HD, NV>(lds_do, rdo, LDK);
-  if (TRR) {
-    tile_write_tr<HD, NV>(lds_qt, rq);
-    tile_write_tr<HD, NV>(lds_dot, rdo);
-  } else {
-    tile_write_t<HD, NV>(lds_qt, rq);
-    tile_write_t<HD, NV>(lds_dot, rdo);
-  }
-  if (first_qt + 1 < n_q_tiles) {
-    tile_load_regs<HD, NV>(rq, qp, (first_qt + 1) * TILE, S, hd, ld);
-    tile_load_regs<HD, NV>(rdo, dop, (first_qt + 1) * TILE, S, hd, ld);
-  }
-  __syncthreads();
+  const int reps = GQA ? n_rep : 1;
+  for (int rep = 0; rep < reps; ++rep) {
+    // this query head's q/dO/lse/delta; lse and delta are [B, nh, S]
+    const int h = hk * n_rep + rep;
+    const long base = GQA ? (long)bi * bst + (long)h * hst : base_kv;
+    const long bh_q = GQA ? (long)bi * nh + h : (long)bh;
+    const __hip_bfloat16* qp = q + base;
+    const __hip_bfloat16* dop = dout + base;
+    const float* lsep = lse + bh_q * S;
+    const float* deltap = delta + bh_q * S;
 
-  for (int qt = first_qt; qt < n_q_tiles; ++qt) {
-    const int cur = qt & 1;
-    const int q0 = qt * TILE;
-    const __bf16* qb = lds_q + cur * TILE * LDK;
-    const __bf16* dob = lds_do + cur * TILE * LDK;
-    const __bf16* qtb = lds_qt + cur * HD * TILE;
-    const __bf16* dotb = lds_dot + cur * HD * TILE;
-
-    // per-32-q subtile: halves the live P/dS registers and loads lse/delta
-    // one quad at a time — this is what keeps the hd64 kernel from spilling
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const int q0s = q0 + 32 * t;
-      const bool edge_t = (q0s < kv_start + 255) || (q0s + 32 > S);
-
-      float pt_val[16], dst_val[16];
-      __builtin_amdgcn_s_setprio(1);
-      {
-        f32x16 sa = (f32x16)(0.f), dpa = (f32x16)(0.f);
-#pragma unroll
-        for (int ks = 0; ks < KSTEPS; ++ks) {
-          const int c0 = ks * 16 + hi * 8;
-          sa = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-              lds_frag(qb, 32 * t + (lane & 31), c0, LDK), kf[ks], sa, 0, 0, 0);
-          dpa = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-              lds_frag(dob, 32 * t + (lane & 31), c0, LDK), vf[ks], dpa, 0, 0, 0);
-        }
-#pragma unroll
-        for (int qd = 0; qd < 4; ++qd) {
-          // lse/delta for this C-layout row quad (q-contiguous)
-          const long qrow = q0s + 8 * qd + 4 * hi;
-          const f32x4 lse4 = load_f32x4_guard(lsep, qrow, S);
-          const f32x4 dl4 = load_f32x4_guard(deltap, qrow, S);
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const int r = 4 * qd + i;
-            const float lse2 = lse4[i] * LOG2E;
-            float p;
-            if (edge_t) {
-              const int q_abs_r = q0s + (r & 3) + 8 * (r >> 2) + 4 * hi;
-              p = (q_abs_r >= kv_abs && q_abs_r < S && kv_abs < S)
-                      ? exp2f(sa[r] * sc2 - lse2) : 0.f;
-            } else {
-              p = exp2f(sa[r] * sc2 - lse2);
-            }
-            pt_val[r] = p;
-            dst_val[r] = p * (dpa[r] - dl4[i]) * scale;
-          }
-        }
-      }
-      __builtin_amdgcn_s_setprio(0);
-
-      if (t == 0 && qt + 1 < n_q_tiles) {
-        tile_write_rows<HD, NV>(lds_q + (cur ^ 1) * TILE * LDK, rq, LDK);
-        tile_write_rows<HD, NV>(lds_do + (cur ^ 1) * TILE * LDK, rdo, LDK);
-        if (TRR) {
-          tile_write_tr<HD, NV>(lds_qt + (cur ^ 1) * HD * TILE, rq);
-          tile_write_tr<HD, NV>(lds_dot + (cur ^ 1) * HD * TILE, rdo);
-        } else {
-          tile_write_t<HD, NV>(lds_qt + (cur ^ 1) * HD * TILE, rq);
-          tile_write_t<HD, NV>(lds_dot + (cur ^ 1) * HD * TILE, rdo);
-        }
-        if (qt + 2 < n_q_tiles) {
-          tile_load_regs<HD, NV>(rq, qp, (qt + 2) * TILE, S, hd, ld);
-          tile_load_regs<HD, NV>(rdo, dop, (qt + 2) * TILE, S, hd, ld);
-        }
-      }
-
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int g = 0; g < 2; ++g) {
-        const bf16x8 pa = pack_p_frag(pt_val, g);
-        const bf16x8 dsa = pack_p_frag(dst_val, g);
-        const int s = 2 * t + g;
-#pragma unroll
-        for (int ht = 0; ht < NT32; ++ht) {
-          const bf16x8 dof = TRR ? tr_frag<HD>(dotb, ht * 32, s * 16, lane)
-                                 : ldsT_frag(dotb, ht * 32 + (lane & 31), s * 16 + hi * 8);
-          const bf16x8 qf2 = TRR ? tr_frag<HD>(qtb, ht * 32, s * 16, lane)
-                                 : ldsT_frag(qtb, ht * 32 + (lane & 31), s * 16 + hi * 8);
-          dv_acc[ht] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa, dof, dv_acc[ht], 0, 0, 0);
-          dk_acc[ht] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dsa, qf2, dk_acc[ht], 0, 0, 0);
-        }
-      }
-      __builtin_amdgcn_s_setprio(0);
+    // restart the two-stage Q/dO pipeline for this head; the barrier keeps
+    // the prologue's LDS writes behind the previous head's last tile reads
+    if (GQA && rep > 0) __syncthreads();
+    tile_load_regs<HD, NV>(rq, qp, first_qt * TILE, S, hd, ld);
+    tile_load_regs<HD, NV>(rdo, dop, first_qt * TILE, S, hd, ld);
+    tile_write_rows<HD, NV>(lds_q, rq, LDK);
+    tile_write_rows<HD, NV>(lds_do, rdo, LDK);
+    if (TRR) {
+      tile_write_tr<HD, NV>(lds_qt, rq);
+      tile_write_tr<HD, NV>(lds_dot, rdo);
+    } else {
+      tile_write_t<HD, NV>(lds_qt, rq);
+      tile_write_t<HD, NV>(lds_dot, rdo);
+    }
+    if (first_qt + 1 < n_q_tiles) {
+      tile_load_regs<HD, NV>(rq, qp, (first_qt + 1) * TILE, S, hd, ld);
+      tile_load_regs<HD, NV>(rdo, dop, (first_qt + 1) * TILE, S, hd, ld);
     }
     __syncthreads();
+
+    for (int qt = first_qt; qt < n_q_tiles; ++qt) {
+      const int cur = qt & 1;
+      const int q0 = qt * TILE;
+      const __bf16* qb = lds_q + cur * TILE * LDK;
+      const __bf16* dob = lds_do + cur * TILE * LDK;
+      const __bf16* qtb = lds_qt + cur * HD * TILE;
+      const __bf16* dotb = lds_dot + cur * HD * TILE;
+
+      // per-32-q subtile: halves the live P/dS registers and loads lse/delta
+      // one quad at a time — this is what keeps the hd64 kernel from spilling
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const int q0s = q0 + 32 * t;
+        const bool edge_t = (q0s < kv_start + 255) || (q0s + 32 > S);
+
+        float pt_val[16], dst_val[16];
+        __builtin_amdgcn_s_setprio(1);
+        {
+          f32x16 sa = (f32x16)(0.f), dpa = (f32x16)(0.f);
+#pragma unroll
+          for (int ks = 0; ks < KSTEPS; ++ks) {
+            const int c0 = ks * 16 + hi * 8;
+            sa = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+                lds_frag(qb, 32 * t + (lane & 31), c0, LDK), kf[ks], sa, 0, 0, 0);
+            dpa = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+                lds_frag(dob, 32 * t + (lane & 31), c0, LDK), vf[ks], dpa, 0, 0, 0);
+          }
+#pragma unroll
+          for (int qd = 0; qd < 4; ++qd) {
+            // lse/delta for this C-layout row quad (q-contiguous)
+            const long qrow = q0s + 8 * qd + 4 * hi;
+            const f32x4 lse4 = load_f32x4_guard(lsep, qrow, S);
+            const f32x4 dl4 = load_f32x4_guard(deltap, qrow, S);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+              const int r = 4 * qd + i;
+              const float lse2 = lse4[i] * LOG2E;
+              float p;
+              if (edge_t) {
+                const int q_abs_r = q0s + (r & 3) + 8 * (r >> 2) + 4 * hi;
+                p = (q_abs_r >= kv_abs && q_abs_r < S && kv_abs < S)
+                        ? exp2f(sa[r] * sc2 - lse2) : 0.f;
+              } else {
+                p = exp2f(sa[r] * sc2 - lse2);
+              }
+              pt_val[r] = p;
+              dst_val[r] = p * (dpa[r] - dl4[i]) * scale;
+            }
+          }
+        }
+        __builtin_amdgcn_s_setprio(0);
+
+        if (t == 0 && qt + 1 < n_q_tiles) {
+          tile_write_rows<HD, NV>(lds_q + (cur ^ 1) * TILE * LDK, rq, LDK);
+          tile_write_rows<HD, NV>(lds_do + (cur ^ 1) * TILE * LDK, rdo, LDK);
+          if (TRR) {
+            tile_write_tr<HD, NV>(lds_qt + (cur ^ 1) * HD * TILE, rq);
+            tile_write_tr<HD, NV>(lds_dot + (cur ^ 1) * HD * TILE, rdo);
+          } else {
+            tile_write_t<HD, NV>(lds_qt + (cur ^ 1) * HD * TILE, rq);
+            tile_write_t<HD, NV>(lds_dot + (cur ^ 1) * HD * TILE, rdo);
+          }
+          if (qt + 2 < n_q_tiles) {
+            tile_load_regs<HD, NV>(rq, qp, (qt + 2) * TILE, S, hd, ld);
+            tile_load_regs<HD, NV>(rdo, dop, (qt + 2) * TILE, S, hd, ld);
+          }
+        }
+
+        __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+          const bf16x8 pa = pack_p_frag(pt_val, g);
+          const bf16x8 dsa = pack_p_frag(dst_val, g);
+          const int s = 2 * t + g;
+#pragma unroll
+          for (int ht = 0; ht < NT32; ++ht) {
+            const bf16x8 dof = TRR ? tr_frag<HD>(dotb, ht * 32, s * 16, lane)
+                                   : ldsT_frag(dotb, ht * 32 + (lane & 31), s * 16 + hi * 8);
+            const bf16x8 qf2 = TRR ? tr_frag<HD>(qtb, ht * 32, s * 16, lane)
+                                   : ldsT_frag(qtb, ht * 32 + (lane & 31), s * 16 + hi * 8);
+            dv_acc[ht] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa, dof, dv_acc[ht], 0, 0, 0);
+            dk_acc[ht] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dsa, qf2, dk_acc[ht], 0, 0, 0);
+          }
+        }
+        __builtin_amdgcn_s_setprio(0);
+      }
+      __syncthreads();
+    }
   }
 
   // epilogue: lane holds one hd column x 16 kv rows per 32-tile
@@ -1052,8 +1086,8 @@ __global__ __launch_bounds__(512) void attn_bwd_dkdv_v3_kernel(
     for (int r = 0; r < 16; ++r) {
       const int kv_row = kv_start + wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
       if (kv_row < S) {
-        dk[base + (long)kv_row * ld + hd_c] = __float2bfloat16(dk_acc[ht][r]);
-        dv[base + (long)kv_row * ld + hd_c] = __float2bfloat16(dv_acc[ht][r]);
+        dk[base_kv + (long)kv_row * ldk + hd_c] = __float2bfloat16(dk_acc[ht][r]);
+        dv[base_kv + (long)kv_row * ldk + hd_c] = __float2bfloat16(dv_acc[ht][r]);
       }
     }
   }
@@ -1063,13 +1097,13 @@ __global__ __launch_bounds__(512) void attn_bwd_dkdv_v3_kernel(
 // backward: dQ kernel — blocks over 128 q rows, kv tiles of 64
 // ---------------------------------------------------------------------------
 
-template <int HD>
+template <int HD, bool GQA = false>
 __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(
     const __hip_bfloat16* __restrict__ q, const __hip_bfloat16* __restrict__ k,
     const __hip_bfloat16* __restrict__ v, const __hip_bfloat16* __restrict__ dout,
     const float* __restrict__ lse, const float* __restrict__ delta,
     __hip_bfloat16* __restrict__ dq, int S, int hd, int nh, long bst, long hst,
-    int ld, float scale) {
+    int ld, long bst_kv, long hst_kv, int ld_kv, int n_rep, float scale) {
   constexpr int KFRAGS = HD / 32;
   constexpr int NT_HD = HD / 16;
   constexpr int LDK = HD + LPAD;
@@ -1085,9 +1119,13 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(
   const int bh = blockIdx.y;
   const int q_start = (gridDim.x - 1 - blockIdx.x) * 128;  // heavy blocks first
   const long base = (long)(bh / nh) * bst + (long)(bh % nh) * hst;
+  // query head h reads kv head h / n_rep through the kv stride triple
+  const long base_kv = GQA ? (long)(bh / nh) * bst_kv + (long)((bh % nh) / n_rep) * hst_kv
+                           : base;
+  const int ldk = GQA ? ld_kv : ld;
   const __hip_bfloat16* qp = q + base;
-  const __hip_bfloat16* kp = k + base;
-  const __hip_bfloat16* vp = v + base;
+  const __hip_bfloat16* kp = k + base_kv;
+  const __hip_bfloat16* vp = v + base_kv;
   const __hip_bfloat16* dop = dout + base;
 
   const int lane = threadIdx.x & 63;
@@ -1119,14 +1157,14 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(
   const int n_tiles = (q_max_abs / TILE) + 1;
 
   bf16x8 rk[NV], rv[NV];
-  tile_load_regs<HD, NV>(rk, kp, 0, S, hd, ld);
-  tile_load_regs<HD, NV>(rv, vp, 0, S, hd, ld);
+  tile_load_regs<HD, NV>(rk, kp, 0, S, hd, ldk);
+  tile_load_regs<HD, NV>(rv, vp, 0, S, hd, ldk);
   tile_write_rows<HD, NV>(lds_k, rk, LDK);
   tile_write_rows<HD, NV>(lds_v, rv, LDK);
   tile_write_t<HD, NV>(lds_kt, rk);
   if (n_tiles > 1) {
-    tile_load_regs<HD, NV>(rk, kp, TILE, S, hd, ld);
-    tile_load_regs<HD, NV>(rv, vp, TILE, S, hd, ld);
+    tile_load_regs<HD, NV>(rk, kp, TILE, S, hd, ldk);
+    tile_load_regs<HD, NV>(rv, vp, TILE, S, hd, ldk);
   }
   __syncthreads();
 
@@ -1172,8 +1210,8 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(
       tile_write_rows<HD, NV>(lds_v + (cur ^ 1) * TILE * LDK, rv, LDK);
       tile_write_t<HD, NV>(lds_kt + (cur ^ 1) * HD * TILE, rk);
       if (kt + 2 < n_tiles) {
-        tile_load_regs<HD, NV>(rk, kp, (kt + 2) * TILE, S, hd, ld);
-        tile_load_regs<HD, NV>(rv, vp, (kt + 2) * TILE, S, hd, ld);
+        tile_load_regs<HD, NV>(rk, kp, (kt + 2) * TILE, S, hd, ldk);
+        tile_load_regs<HD, NV>(rv, vp, (kt + 2) * TILE, S, hd, ldk);
       }
     }
 
@@ -1215,13 +1253,14 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(
 // backward: dK/dV kernel — blocks over 128 kv rows, q tiles of 64
 // ---------------------------------------------------------------------------
 
-template <int HD>
+template <int HD, bool GQA = false>
 __global__ __launch_bounds__(512) void attn_bwd_dkdv_kernel(
     const __hip_bfloat16* __restrict__ q, const __hip_bfloat16* __restrict__ k,
     const __hip_bfloat16* __restrict__ v, const __hip_bfloat16* __restrict__ dout,
     const float* __restrict__ lse, const float* __restrict__ delta,
     __hip_bfloat16* __restrict__ dk, __hip_bfloat16* __restrict__ dv,
-    int S, int hd, int nh, long bst, long hst, int ld, float scale) {
+    int S, int hd, int nh, long bst, long hst, int ld, long bst_kv, long hst_kv,
+    int ld_kv, int n_rep, float scale) {
   constexpr int KFRAGS = HD / 32;
   constexpr int NT_HD = HD / 16;
   constexpr int LDK = HD + LPAD;
@@ -1240,11 +1279,16 @@ __global__ __launch_bounds__(512) void attn_bwd_dkdv_kernel(
 
   const int bh = blockIdx.y;
   const int kv_start_blk = blockIdx.x * 128;
-  const long base = (long)(bh / nh) * bst + (long)(bh % nh) * hst;
-  const __hip_bfloat16* qp = q + base;
-  const __hip_bfloat16* kp = k + base;
-  const __hip_bfloat16* vp = v + base;
-  const __hip_bfloat16* dop = dout + base;
+  // see attn_bwd_dkdv_v3_kernel: GQA blocks are (b, kv head) and loop over
+  // the group's query heads
+  const int nkv = GQA ? nh / n_rep : nh;
+  const int bi = bh / nkv;
+  const int hk = bh % nkv;
+  const long base_kv = GQA ? (long)bi * bst_kv + (long)hk * hst_kv
+                           : (long)(bh / nh) * bst + (long)(bh % nh) * hst;
+  const int ldk = GQA ? ld_kv : ld;
+  const __hip_bfloat16* kp = k + base_kv;
+  const __hip_bfloat16* vp = v + base_kv;
 
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -1255,8 +1299,8 @@ __global__ __launch_bounds__(512) void attn_bwd_dkdv_kernel(
   bf16x8 kfrag[KFRAGS], vfrag[KFRAGS];
 #pragma unroll
   for (int kf = 0; kf < KFRAGS; ++kf) {
-    kfrag[kf] = global_frag(kp, kvrow_abs, S, hd, ld, kf * 32 + kgrp * 8);
-    vfrag[kf] = global_frag(vp, kvrow_abs, S, hd, ld, kf * 32 + kgrp * 8);
+    kfrag[kf] = global_frag(kp, kvrow_abs, S, hd, ldk, kf * 32 + kgrp * 8);
+    vfrag[kf] = global_frag(vp, kvrow_abs, S, hd, ldk, kf * 32 + kgrp * 8);
   }
 
   f32x4 dk_acc[NT_HD], dv_acc[NT_HD];
@@ -1270,109 +1314,122 @@ __global__ __launch_bounds__(512) void attn_bwd_dkdv_kernel(
   const int n_q_tiles = (S + TILE - 1) / TILE;
 
   bf16x8 rq[NV], rdo[NV];
-  tile_load_regs<HD, NV>(rq, qp, first_qt * TILE, S, hd, ld);
-  tile_load_regs<HD, NV>(rdo, dop, first_qt * TILE, S, hd, ld);
-  tile_write_rows<HD, NV>(lds_q, rq, LDK);
-  tile_write_rows<HD, NV>(lds_do, rdo, LDK);
-  tile_write_t<HD, NV>(lds_qt, rq);
-  tile_write_t<HD, NV>(lds_dot, rdo);
-  if (first_qt + 1 < n_q_tiles) {
-    tile_load_regs<HD, NV>(rq, qp, (first_qt + 1) * TILE, S, hd, ld);
-    tile_load_regs<HD, NV>(rdo, dop, (first_qt + 1) * TILE, S, hd, ld);
-  }
-  __syncthreads();
+  const int reps = GQA ? n_rep : 1;
+  for (int rep = 0; rep < reps; ++rep) {
+    // this query head's q/dO/lse/delta; lse and delta are [B, nh, S]
+    const int h = hk * n_rep + rep;
+    const long base = GQA ? (long)bi * bst + (long)h * hst : base_kv;
+    const long bh_q = GQA ? (long)bi * nh + h : (long)bh;
+    const __hip_bfloat16* qp = q + base;
+    const __hip_bfloat16* dop = dout + base;
 
-  for (int qt = first_qt; qt < n_q_tiles; ++qt) {
-    const int cur = (NBUF == 2) ? (qt & 1) : 0;
-    const int q_start = qt * TILE;
-    const __bf16* qb = lds_q + cur * TILE * LDK;
-    const __bf16* dob = lds_do + cur * TILE * LDK;
-    const __bf16* qtb = lds_qt + cur * HD * TILE;
-    const __bf16* dotb = lds_dot + cur * HD * TILE;
-    const bool edge = (q_start < kv_start_blk + 127) || (q_start + TILE > S);
-
-    // T = K Q^T (scores transposed), dPT = V dO^T
-    float pt_val[4][4], dst_val[4][4];
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int n = 0; n < 4; ++n) {
-      f32x4 t_acc = {0.f, 0.f, 0.f, 0.f};
-      f32x4 dpt_acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int kf = 0; kf < KFRAGS; ++kf) {
-        t_acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            kfrag[kf], lds_frag(qb, n * 16 + col, kf * 32 + kgrp * 8, LDK), t_acc, 0, 0, 0);
-        dpt_acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            vfrag[kf], lds_frag(dob, n * 16 + col, kf * 32 + kgrp * 8, LDK), dpt_acc, 0, 0, 0);
-      }
-      const int q_abs = q_start + n * 16 + col;
-      const float lse_c = (q_abs < S) ? lse[(long)bh * S + q_abs] : 0.f;
-      const float delta_c = (q_abs < S) ? delta[(long)bh * S + q_abs] : 0.f;
-#pragma unroll
-      for (int reg = 0; reg < 4; ++reg) {
-        float p;
-        if (edge) {
-          const int kv_abs = kv_start_blk + wave * 16 + kgrp * 4 + reg;
-          p = (q_abs >= kv_abs && q_abs < S && kv_abs < S)
-                  ? __expf(t_acc[reg] * scale - lse_c) : 0.f;
-        } else {
-          p = __expf(t_acc[reg] * scale - lse_c);
-        }
-        pt_val[n][reg] = p;
-        dst_val[n][reg] = p * (dpt_acc[reg] - delta_c) * scale;
-      }
+    // restart the two-stage Q/dO pipeline for this head; the barrier keeps
+    // the prologue's LDS writes behind the previous head's last tile reads
+    if (GQA && rep > 0) __syncthreads();
+    tile_load_regs<HD, NV>(rq, qp, first_qt * TILE, S, hd, ld);
+    tile_load_regs<HD, NV>(rdo, dop, first_qt * TILE, S, hd, ld);
+    tile_write_rows<HD, NV>(lds_q, rq, LDK);
+    tile_write_rows<HD, NV>(lds_do, rdo, LDK);
+    tile_write_t<HD, NV>(lds_qt, rq);
+    tile_write_t<HD, NV>(lds_dot, rdo);
+    if (first_qt + 1 < n_q_tiles) {
+      tile_load_regs<HD, NV>(rq, qp, (first_qt + 1) * TILE, S, hd, ld);
+      tile_load_regs<HD, NV>(rdo, dop, (first_qt + 1) * TILE, S, hd, ld);
     }
-    __builtin_amdgcn_s_setprio(0);
-
-    if (NBUF == 2 && qt + 1 < n_q_tiles) {  // overlapped staging, mid-compute
-      tile_write_rows<HD, NV>(lds_q + (cur ^ 1) * TILE * LDK, rq, LDK);
-      tile_write_rows<HD, NV>(lds_do + (cur ^ 1) * TILE * LDK, rdo, LDK);
-      tile_write_t<HD, NV>(lds_qt + (cur ^ 1) * HD * TILE, rq);
-      tile_write_t<HD, NV>(lds_dot + (cur ^ 1) * HD * TILE, rdo);
-      if (qt + 2 < n_q_tiles) {
-        tile_load_regs<HD, NV>(rq, qp, (qt + 2) * TILE, S, hd, ld);
-        tile_load_regs<HD, NV>(rdo, dop, (qt + 2) * TILE, S, hd, ld);
-      }
-    }
-
-    // write BOTH relayouts up front into separate per-wave regions, then run
-    // both MFMA groups back-to-back: one lgkm boundary and no
-    // write-after-read stall between the dV and dK passes
-    __bf16* pw = lds_p + wave * 16 * LDT;
-    __bf16* pw2 = lds_p2 + wave * 16 * LDT;
-#pragma unroll
-    for (int n = 0; n < 4; ++n)
-#pragma unroll
-      for (int reg = 0; reg < 4; ++reg) {
-        pw[lds_rm_idx(kgrp * 4 + reg, n * 16 + col, LDT)] = (__bf16)pt_val[n][reg];
-        pw2[lds_rm_idx(kgrp * 4 + reg, n * 16 + col, LDT)] = (__bf16)dst_val[n][reg];
-      }
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      const bf16x8 a = lds_frag(pw, col, ks * 32 + kgrp * 8, LDT);
-      const bf16x8 a2 = lds_frag(pw2, col, ks * 32 + kgrp * 8, LDT);
-#pragma unroll
-      for (int t = 0; t < NT_HD; ++t) {
-        dv_acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            a, ldsT_frag(dotb, t * 16 + col, ks * 32 + kgrp * 8), dv_acc[t], 0, 0, 0);
-        dk_acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            a2, ldsT_frag(qtb, t * 16 + col, ks * 32 + kgrp * 8), dk_acc[t], 0, 0, 0);
-      }
-    }
-    __builtin_amdgcn_s_setprio(0);
     __syncthreads();
 
-    if (NBUF == 1 && qt + 1 < n_q_tiles) {
-      tile_write_rows<HD, NV>(lds_q, rq, LDK);
-      tile_write_rows<HD, NV>(lds_do, rdo, LDK);
-      tile_write_t<HD, NV>(lds_qt, rq);
-      tile_write_t<HD, NV>(lds_dot, rdo);
-      if (qt + 2 < n_q_tiles) {
-        tile_load_regs<HD, NV>(rq, qp, (qt + 2) * TILE, S, hd, ld);
-        tile_load_regs<HD, NV>(rdo, dop, (qt + 2) * TILE, S, hd, ld);
+    for (int qt = first_qt; qt < n_q_tiles; ++qt) {
+      const int cur = (NBUF == 2) ? (qt & 1) : 0;
+      const int q_start = qt * TILE;
+      const __bf16* qb = lds_q + cur * TILE * LDK;
+      const __bf16* dob = lds_do + cur * TILE * LDK;
+      const __bf16* qtb = lds_qt + cur * HD * TILE;
+      const __bf16* dotb = lds_dot + cur * HD * TILE;
+      const bool edge = (q_start < kv_start_blk + 127) || (q_start + TILE > S);
+
+      // T = K Q^T (scores transposed), dPT = V dO^T
+      float pt_val[4][4], dst_val[4][4];
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int n = 0; n < 4; ++n) {
+        f32x4 t_acc = {0.f, 0.f, 0.f, 0.f};
+        f32x4 dpt_acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int kf = 0; kf < KFRAGS; ++kf) {
+          t_acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              kfrag[kf], lds_frag(qb, n * 16 + col, kf * 32 + kgrp * 8, LDK), t_acc, 0, 0, 0);
+          dpt_acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              vfrag[kf], lds_frag(dob, n * 16 + col, kf * 32 + kgrp * 8, LDK), dpt_acc, 0, 0, 0);
+        }
+        const int q_abs = q_start + n * 16 + col;
+        const float lse_c = (q_abs < S) ? lse[bh_q * S + q_abs] : 0.f;
+        const float delta_c = (q_abs < S) ? delta[bh_q * S + q_abs] : 0.f;
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+          float p;
+          if (edge) {
+            const int kv_abs = kv_start_blk + wave * 16 + kgrp * 4 + reg;
+            p = (q_abs >= kv_abs && q_abs < S && kv_abs < S)
+                    ? __expf(t_acc[reg] * scale - lse_c) : 0.f;
+          } else {
+            p = __expf(t_acc[reg] * scale - lse_c);
+          }
+          pt_val[n][reg] = p;
+          dst_val[n][reg] = p * (dpt_acc[reg] - delta_c) * scale;
+        }
       }
+      __builtin_amdgcn_s_setprio(0);
+
+      if (NBUF == 2 && qt + 1 < n_q_tiles) {  // overlapped staging, mid-compute
+        tile_write_rows<HD, NV>(lds_q + (cur ^ 1) * TILE * LDK, rq, LDK);
+        tile_write_rows<HD, NV>(lds_do + (cur ^ 1) * TILE * LDK, rdo, LDK);
+        tile_write_t<HD, NV>(lds_qt + (cur ^ 1) * HD * TILE, rq);
+        tile_write_t<HD, NV>(lds_dot + (cur ^ 1) * HD * TILE, rdo);
+        if (qt + 2 < n_q_tiles) {
+          tile_load_regs<HD, NV>(rq, qp, (qt + 2) * TILE, S, hd, ld);
+          tile_load_regs<HD, NV>(rdo, dop, (qt + 2) * TILE, S, hd, ld);
+        }
+      }
+
+      // write BOTH relayouts up front into separate per-wave regions, then run
+      // both MFMA groups back-to-back: one lgkm boundary and no
+      // write-after-read stall between the dV and dK passes
+      __bf16* pw = lds_p + wave * 16 * LDT;
+      __bf16* pw2 = lds_p2 + wave * 16 * LDT;
+#pragma unroll
+      for (int n = 0; n < 4; ++n)
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+          pw[lds_rm_idx(kgrp * 4 + reg, n * 16 + col, LDT)] = (__bf16)pt_val[n][reg];
+          pw2[lds_rm_idx(kgrp * 4 + reg, n * 16 + col, LDT)] = (__bf16)dst_val[n][reg];
+        }
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) {
+        const bf16x8 a = lds_frag(pw, col, ks * 32 + kgrp * 8, LDT);
+        const bf16x8 a2 = lds_frag(pw2, col, ks * 32 + kgrp * 8, LDT);
+#pragma unroll
+        for (int t = 0; t < NT_HD; ++t) {
+          dv_acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              a, ldsT_frag(dotb, t * 16 + col, ks * 32 + kgrp * 8), dv_acc[t], 0, 0, 0);
+          dk_acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              a2, ldsT_frag(qtb, t * 16 + col, ks * 32 + kgrp * 8), dk_acc[t], 0, 0, 0);
+        }
+      }
+      __builtin_amdgcn_s_setprio(0);
       __syncthreads();
+
+      if (NBUF == 1 && qt + 1 < n_q_tiles) {
+        tile_write_rows<HD, NV>(lds_q, rq, LDK);
+        tile_write_rows<HD, NV>(lds_do, rdo, LDK);
+        tile_write_t<HD, NV>(lds_qt, rq);
+        tile_write_t<HD, NV>(lds_dot, rdo);
+        if (qt + 2 < n_q_tiles) {
+          tile_load_regs<HD, NV>(rq, qp, (qt + 2) * TILE, S, hd, ld);
+          tile_load_regs<HD, NV>(rdo, dop, (qt + 2) * TILE, S, hd, ld);
+        }
+        __syncthreads();
+      }
     }
   }
 
@@ -1384,8 +1441,8 @@ __global__ __launch_bounds__(512) void attn_bwd_dkdv_kernel(
     for (int t = 0; t < NT_HD; ++t) {
       const int c = t * 16 + col;
       if (c < hd) {
-        dk[base + (long)row_abs * ld + c] = __float2bfloat16(dk_acc[t][reg]);
-        dv[base + (long)row_abs * ld + c] = __float2bfloat16(dv_acc[t][reg]);
+        dk[base_kv + (long)row_abs * ldk + c] = __float2bfloat16(dk_acc[t][reg]);
+        dv[base_kv + (long)row_abs * ldk + c] = __float2bfloat16(dv_acc[t][reg]);
       }
     }
   }
@@ -1432,25 +1489,77 @@ static std::array<long, 3> attn_strides(const torch::Tensor& q) {
   return {q.stride(0), q.stride(1), q.stride(2)};
 }
 
-static bool same_strides(const torch::Tensor& a, const torch::Tensor& b) {
-  return a.strides() == b.strides();
+// strides compared only where they address something (a size-1 dim's
+// stride is arbitrary: one kv head, or batch 1)
+static bool same_layout(const torch::Tensor& a, const torch::Tensor& b) {
+  if (a.sizes() != b.sizes()) return false;
+  for (int d = 0; d < a.dim(); ++d)
+    if (a.size(d) > 1 && a.stride(d) != b.stride(d)) return false;
+  return true;
 }
+
+// Launch geometry shared by forward and backward.  q is [B, nh, S, hd]; k
+// and v are [B, nkv, S, hd] with nh % nkv == 0 (grouped-query attention:
+// query head h reads kv head h / n_rep).  Each side has its own stride
+// triple; k and v share one.  `gqa` selects the kernels' two-triple
+// instantiations — the plain multi-head call keeps the single-base code.
+struct AttnGeom {
+  long bst, hst;
+  int ld;
+  long bst_kv, hst_kv;
+  int ld_kv, n_rep;
+  bool gqa;
+};
+
+static AttnGeom attn_geometry(const torch::Tensor& q, const torch::Tensor& k,
+                              const torch::Tensor& v) {
+  TORCH_CHECK(q.is_cuda() && q.dim() == 4, "attention: q must be a 4-d device tensor");
+  TORCH_CHECK(q.scalar_type() == torch::kBFloat16, "attn kernels are bf16-only");
+  TORCH_CHECK(k.is_cuda() && v.is_cuda() && k.dim() == 4 && v.dim() == 4,
+              "attention: k/v must be 4-d device tensors");
+  TORCH_CHECK(k.scalar_type() == torch::kBFloat16 && v.scalar_type() == torch::kBFloat16,
+              "attn kernels are bf16-only");
+  TORCH_CHECK(k.sizes() == v.sizes(), "attention: k and v must have the same shape");
+  TORCH_CHECK(k.size(0) == q.size(0) && k.size(2) == q.size(2) && k.size(3) == q.size(3),
+              "attention: q and k/v must agree on batch, sequence and head_dim, got q ",
+              q.sizes(), " k ", k.sizes());
+  const long nh = q.size(1), nkv = k.size(1);
+  TORCH_CHECK(nkv >= 1 && nh % nkv == 0,
+              "attention: kv heads (", nkv, ") must divide query heads (", nh, ")");
+  const auto sq = attn_strides(q);
+  const auto sk = attn_strides(k);
+  attn_strides(v);
+  TORCH_CHECK(same_layout(k, v), "attention: k and v must share a layout");
+  AttnGeom g;
+  g.bst = sq[0]; g.hst = sq[1]; g.ld = (int)sq[2];
+  g.bst_kv = sk[0]; g.hst_kv = sk[1]; g.ld_kv = (int)sk[2];
+  g.n_rep = (int)(nh / nkv);
+  g.gqa = (g.n_rep != 1) || !same_layout(q, k);
+  return g;
+}
+
+// call f with std::true_type for the kv-strided (GQA) instantiations, else
+// std::false_type
+template <typename F>
+static void with_gqa(bool gqa, F&& f) {
+  if (gqa) f(std::true_type{});
+  else f(std::false_type{});
+}
+
+#define BF(t) ((const __hip_bfloat16*)(t).data_ptr())
+#define GEOM_ARGS g.bst, g.hst, g.ld, g.bst_kv, g.hst_kv, g.ld_kv, g.n_rep, (float)scale
 
 std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor v,
                                     double scale) {
-  TORCH_CHECK(q.is_cuda() && q.dim() == 4);
-  TORCH_CHECK(q.scalar_type() == torch::kBFloat16, "attn kernels are bf16-only");
+  const AttnGeom g = attn_geometry(q, k, v);
   const int B = q.size(0), nh = q.size(1), S = q.size(2), hd = q.size(3);
   const int HDP = pad32(hd);
-  const auto st = attn_strides(q);
-  TORCH_CHECK(same_strides(q, k) && same_strides(q, v),
-              "q/k/v must share a layout");
-  const long bst = st[0], hst = st[1];
-  const int ld = (int)st[2];
   auto out = torch::empty_strided(q.sizes(), q.strides(), q.options());
   auto lse = torch::empty({B, nh, S}, q.options().dtype(torch::kFloat32));
   auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
   dim3 block(512);
+#define FWD_ARGS BF(q), BF(k), BF(v), (__hip_bfloat16*)out.data_ptr(), \
+                 lse.data_ptr<float>(), S, hd, nh, GEOM_ARGS
   if (attn_fwd_version() == 3) {
     DISPATCH_HD(HDP, {
       dim3 grid((S + 255) / 256, B * nh);
@@ -1464,22 +1573,18 @@ std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k, torch::Ten
         const char* e = getenv("RELORA_AMD_ATTN_TR_FWD");
         return !(e && e[0] == '0');  // default ON: fwd PV tr-read measured +12%
       }();
-      if (occ4 && HD <= 64 && trrf) {
-        hipLaunchKernelGGL((attn_fwd_v3_kernel<HD, 4, true>), grid, block, smem, stream,
-                           (const __hip_bfloat16*)q.data_ptr(), (const __hip_bfloat16*)k.data_ptr(),
-                           (const __hip_bfloat16*)v.data_ptr(), (__hip_bfloat16*)out.data_ptr(),
-                           lse.data_ptr<float>(), S, hd, nh, bst, hst, ld, (float)scale);
-      } else if (occ4 && HD <= 64) {
-        hipLaunchKernelGGL((attn_fwd_v3_kernel<HD, 4>), grid, block, smem, stream,
-                           (const __hip_bfloat16*)q.data_ptr(), (const __hip_bfloat16*)k.data_ptr(),
-                           (const __hip_bfloat16*)v.data_ptr(), (__hip_bfloat16*)out.data_ptr(),
-                           lse.data_ptr<float>(), S, hd, nh, bst, hst, ld, (float)scale);
-      } else {
-        hipLaunchKernelGGL((attn_fwd_v3_kernel<HD>), grid, block, smem, stream,
-                           (const __hip_bfloat16*)q.data_ptr(), (const __hip_bfloat16*)k.data_ptr(),
-                           (const __hip_bfloat16*)v.data_ptr(), (__hip_bfloat16*)out.data_ptr(),
-                           lse.data_ptr<float>(), S, hd, nh, bst, hst, ld, (float)scale);
-      }
+      with_gqa(g.gqa, [&](auto G) {
+        constexpr bool GQA = decltype(G)::value;
+        if (occ4 && HD <= 64 && trrf)
+          hipLaunchKernelGGL((attn_fwd_v3_kernel<HD, 4, true, GQA>), grid, block, smem,
+                             stream, FWD_ARGS);
+        else if (occ4 && HD <= 64)
+          hipLaunchKernelGGL((attn_fwd_v3_kernel<HD, 4, false, GQA>), grid, block, smem,
+                             stream, FWD_ARGS);
+        else
+          hipLaunchKernelGGL((attn_fwd_v3_kernel<HD, 2, false, GQA>), grid, block, smem,
+                             stream, FWD_ARGS);
+      });
     });
     HIP_CHECK_LAST();
     return {out, lse};
@@ -1489,11 +1594,12 @@ std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k, torch::Ten
     dim3 grid((S + 128 * RF - 1) / (128 * RF), B * nh);
     const int LDK = HD + LPAD, LDP = TILE + LPAD;
     size_t smem = (2 * TILE * LDK + 2 * HD * TILE + RF * 8 * 16 * LDP) * sizeof(__bf16);
-    hipLaunchKernelGGL((attn_fwd_kernel<HD>), grid, block, smem, stream,
-                       (const __hip_bfloat16*)q.data_ptr(), (const __hip_bfloat16*)k.data_ptr(),
-                       (const __hip_bfloat16*)v.data_ptr(), (__hip_bfloat16*)out.data_ptr(),
-                       lse.data_ptr<float>(), S, hd, nh, bst, hst, ld, (float)scale);
+    with_gqa(g.gqa, [&](auto G) {
+      hipLaunchKernelGGL((attn_fwd_kernel<HD, decltype(G)::value>), grid, block, smem,
+                         stream, FWD_ARGS);
+    });
   });
+#undef FWD_ARGS
   HIP_CHECK_LAST();
   return {out, lse};
 }
@@ -1501,29 +1607,33 @@ std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k, torch::Ten
 std::vector<torch::Tensor> attn_bwd(torch::Tensor q, torch::Tensor k, torch::Tensor v,
                                     torch::Tensor o, torch::Tensor lse, torch::Tensor dout,
                                     double scale) {
+  const AttnGeom g = attn_geometry(q, k, v);
   const int B = q.size(0), nh = q.size(1), S = q.size(2), hd = q.size(3);
+  const int nkv = k.size(1);
   const int HDP = pad32(hd);
-  const auto st = attn_strides(q);
-  const long bst = st[0], hst = st[1];
-  const int ld = (int)st[2];
-  // every tensor the kernels touch must share q's layout; copy dout into
-  // it if the incoming grad doesn't (o always does — attn_fwd allocated it)
-  TORCH_CHECK(same_strides(q, k) && same_strides(q, v) && same_strides(q, o));
-  if (!(dout.stride(3) == 1 && same_strides(q, dout))) {
+  // the query-side tensors must share q's layout; copy dout into it if the
+  // incoming grad doesn't (o always does — attn_fwd allocated it)
+  TORCH_CHECK(o.is_cuda() && o.scalar_type() == q.scalar_type() && same_layout(q, o),
+              "attention: o must share q's layout");
+  TORCH_CHECK(lse.is_cuda() && lse.scalar_type() == torch::kFloat32 && lse.is_contiguous() &&
+                  lse.dim() == 3 && lse.size(0) == B && lse.size(1) == nh && lse.size(2) == S,
+              "attention: lse must be contiguous fp32 [B, nh, S]");
+  TORCH_CHECK(dout.sizes() == q.sizes(), "attention: dout must have q's shape");
+  if (!(dout.stride(3) == 1 && same_layout(q, dout) && dout.scalar_type() == q.scalar_type())) {
     auto d2 = torch::empty_strided(q.sizes(), q.strides(), q.options());
     d2.copy_(dout);
     dout = d2;
   }
   auto dq = torch::empty_strided(q.sizes(), q.strides(), q.options());
-  auto dk = torch::empty_strided(q.sizes(), q.strides(), q.options());
-  auto dv = torch::empty_strided(q.sizes(), q.strides(), q.options());
+  auto dk = torch::empty_strided(k.sizes(), k.strides(), k.options());
+  auto dv = torch::empty_strided(k.sizes(), k.strides(), k.options());
   auto delta = torch::empty({B, nh, S}, q.options().dtype(torch::kFloat32));
   auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
 
   const long n_rows = (long)B * nh * S;
   hipLaunchKernelGGL(attn_delta_kernel, dim3((n_rows + 31) / 32), dim3(256), 0, stream,
-                     (const __hip_bfloat16*)dout.data_ptr(), (const __hip_bfloat16*)o.data_ptr(),
-                     delta.data_ptr<float>(), n_rows, hd, nh, S, bst, hst, ld);
+                     BF(dout), BF(o), delta.data_ptr<float>(), n_rows, hd, nh, S,
+                     g.bst, g.hst, g.ld);
   HIP_CHECK_LAST();
 
   // RELORA_AMD_ATTN_BWD=2 falls back to the v2 (16x16 C-layout) backward
@@ -1532,6 +1642,14 @@ std::vector<torch::Tensor> attn_bwd(torch::Tensor q, torch::Tensor k, torch::Ten
     return (e && e[0] == '2') ? 2 : 3;
   }();
 
+#define DQ_ARGS BF(q), BF(k), BF(v), BF(dout), lse.data_ptr<float>(), delta.data_ptr<float>(), \
+                (__hip_bfloat16*)dq.data_ptr(), S, hd, nh, GEOM_ARGS
+#define DKDV_ARGS BF(q), BF(k), BF(v), BF(dout), lse.data_ptr<float>(), delta.data_ptr<float>(), \
+                  (__hip_bfloat16*)dk.data_ptr(), (__hip_bfloat16*)dv.data_ptr(), S, hd, nh,   \
+                  GEOM_ARGS
+  // dK/dV blocks own kv rows: one per (b, kv head) — with GQA each loops
+  // over the n_rep query heads of its group
+  const int dkdv_gy = g.gqa ? B * nkv : B * nh;
   dim3 block(512);
   DISPATCH_HD(HDP, {
     const int LDK = HD + LPAD, LDT = TILE + LPAD;
@@ -1546,40 +1664,25 @@ std::vector<torch::Tensor> attn_bwd(torch::Tensor q, torch::Tensor k, torch::Ten
         const char* e = getenv("RELORA_AMD_DQ_OCC4");
         return e && e[0] == '1';
       }();
-      if (dqocc4 && HD <= 64)
-        hipLaunchKernelGGL((attn_bwd_dq_v3_kernel<HD, 8, 4>), dim3((S + 255) / 256, B * nh),
-                           block, smem_dq3, stream,
-                           (const __hip_bfloat16*)q.data_ptr(), (const __hip_bfloat16*)k.data_ptr(),
-                           (const __hip_bfloat16*)v.data_ptr(), (const __hip_bfloat16*)dout.data_ptr(),
-                           lse.data_ptr<float>(), delta.data_ptr<float>(),
-                           (__hip_bfloat16*)dq.data_ptr(), S, hd, nh, bst, hst, ld,
-                           (float)scale);
-      else if (dq4w && HD <= 64)
-        hipLaunchKernelGGL((attn_bwd_dq_v3_kernel<HD, 4>), dim3((S + 127) / 128, B * nh),
-                           dim3(256), smem_dq3, stream,
-                           (const __hip_bfloat16*)q.data_ptr(), (const __hip_bfloat16*)k.data_ptr(),
-                           (const __hip_bfloat16*)v.data_ptr(), (const __hip_bfloat16*)dout.data_ptr(),
-                           lse.data_ptr<float>(), delta.data_ptr<float>(),
-                           (__hip_bfloat16*)dq.data_ptr(), S, hd, nh, bst, hst, ld,
-                           (float)scale);
-      else
-        hipLaunchKernelGGL((attn_bwd_dq_v3_kernel<HD>), dim3((S + 255) / 256, B * nh), block,
-                           smem_dq3, stream,
-                           (const __hip_bfloat16*)q.data_ptr(), (const __hip_bfloat16*)k.data_ptr(),
-                           (const __hip_bfloat16*)v.data_ptr(), (const __hip_bfloat16*)dout.data_ptr(),
-                           lse.data_ptr<float>(), delta.data_ptr<float>(),
-                           (__hip_bfloat16*)dq.data_ptr(), S, hd, nh, bst, hst, ld,
-                           (float)scale);
+      with_gqa(g.gqa, [&](auto G) {
+        constexpr bool GQA = decltype(G)::value;
+        if (dqocc4 && HD <= 64)
+          hipLaunchKernelGGL((attn_bwd_dq_v3_kernel<HD, 8, 4, GQA>),
+                             dim3((S + 255) / 256, B * nh), block, smem_dq3, stream, DQ_ARGS);
+        else if (dq4w && HD <= 64)
+          hipLaunchKernelGGL((attn_bwd_dq_v3_kernel<HD, 4, 2, GQA>),
+                             dim3((S + 127) / 128, B * nh), dim3(256), smem_dq3, stream, DQ_ARGS);
+        else
+          hipLaunchKernelGGL((attn_bwd_dq_v3_kernel<HD, 8, 2, GQA>),
+                             dim3((S + 255) / 256, B * nh), block, smem_dq3, stream, DQ_ARGS);
+      });
       HIP_CHECK_LAST();
     } else {
       size_t smem_dq = (2 * TILE * LDK * 2 + 2 * HD * TILE + 8 * 16 * LDT) * sizeof(__bf16);
-      hipLaunchKernelGGL((attn_bwd_dq_kernel<HD>), dim3((S + 127) / 128, B * nh), block,
-                         smem_dq, stream,
-                         (const __hip_bfloat16*)q.data_ptr(), (const __hip_bfloat16*)k.data_ptr(),
-                         (const __hip_bfloat16*)v.data_ptr(), (const __hip_bfloat16*)dout.data_ptr(),
-                         lse.data_ptr<float>(), delta.data_ptr<float>(),
-                         (__hip_bfloat16*)dq.data_ptr(), S, hd, nh, bst, hst, ld,
-                         (float)scale);
+      with_gqa(g.gqa, [&](auto G) {
+        hipLaunchKernelGGL((attn_bwd_dq_kernel<HD, decltype(G)::value>),
+                           dim3((S + 127) / 128, B * nh), block, smem_dq, stream, DQ_ARGS);
+      });
       HIP_CHECK_LAST();
     }
     if (bwd_ver == 3 && HD <= 64) {
@@ -1591,36 +1694,31 @@ std::vector<torch::Tensor> attn_bwd(torch::Tensor q, torch::Tensor k, torch::Ten
         return e && e[0] == '1';
       }();
       size_t smem_dkdv3 = (2 * TILE * LDK * 2 + 2 * HD * TILE * 2) * sizeof(__bf16);
-      if (trr)
-        hipLaunchKernelGGL((attn_bwd_dkdv_v3_kernel<HD, true>), dim3((S + 255) / 256, B * nh),
-                           block, smem_dkdv3, stream,
-                           (const __hip_bfloat16*)q.data_ptr(), (const __hip_bfloat16*)k.data_ptr(),
-                           (const __hip_bfloat16*)v.data_ptr(), (const __hip_bfloat16*)dout.data_ptr(),
-                           lse.data_ptr<float>(), delta.data_ptr<float>(),
-                           (__hip_bfloat16*)dk.data_ptr(), (__hip_bfloat16*)dv.data_ptr(),
-                           S, hd, nh, bst, hst, ld, (float)scale);
-      else
-        hipLaunchKernelGGL((attn_bwd_dkdv_v3_kernel<HD>), dim3((S + 255) / 256, B * nh), block,
-                           smem_dkdv3, stream,
-                           (const __hip_bfloat16*)q.data_ptr(), (const __hip_bfloat16*)k.data_ptr(),
-                           (const __hip_bfloat16*)v.data_ptr(), (const __hip_bfloat16*)dout.data_ptr(),
-                           lse.data_ptr<float>(), delta.data_ptr<float>(),
-                           (__hip_bfloat16*)dk.data_ptr(), (__hip_bfloat16*)dv.data_ptr(),
-                           S, hd, nh, bst, hst, ld, (float)scale);
+      with_gqa(g.gqa, [&](auto G) {
+        constexpr bool GQA = decltype(G)::value;
+        if (trr)
+          hipLaunchKernelGGL((attn_bwd_dkdv_v3_kernel<HD, true, GQA>),
+                             dim3((S + 255) / 256, dkdv_gy), block, smem_dkdv3, stream,
+                             DKDV_ARGS);
+        else
+          hipLaunchKernelGGL((attn_bwd_dkdv_v3_kernel<HD, false, GQA>),
+                             dim3((S + 255) / 256, dkdv_gy), block, smem_dkdv3, stream,
+                             DKDV_ARGS);
+      });
       HIP_CHECK_LAST();
     } else {
       constexpr int NBUF = (HD <= 64) ? 2 : 1;
       size_t smem_dkdv =
           (NBUF * TILE * LDK * 2 + NBUF * HD * TILE * 2 + 2 * 8 * 16 * LDT) * sizeof(__bf16);
-      hipLaunchKernelGGL((attn_bwd_dkdv_kernel<HD>), dim3((S + 127) / 128, B * nh), block,
-                         smem_dkdv, stream,
-                         (const __hip_bfloat16*)q.data_ptr(), (const __hip_bfloat16*)k.data_ptr(),
-                         (const __hip_bfloat16*)v.data_ptr(), (const __hip_bfloat16*)dout.data_ptr(),
-                         lse.data_ptr<float>(), delta.data_ptr<float>(),
-                         (__hip_bfloat16*)dk.data_ptr(), (__hip_bfloat16*)dv.data_ptr(),
-                         S, hd, nh, bst, hst, ld, (float)scale);
+      with_gqa(g.gqa, [&](auto G) {
+        hipLaunchKernelGGL((attn_bwd_dkdv_kernel<HD, decltype(G)::value>),
+                           dim3((S + 127) / 128, dkdv_gy), block, smem_dkdv, stream,
+                           DKDV_ARGS);
+      });
       HIP_CHECK_LAST();
     }
   });
+#undef DQ_ARGS
+#undef DKDV_ARGS
   return {dq, dk, dv};
 }

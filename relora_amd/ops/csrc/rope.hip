@@ -108,8 +108,13 @@ std::vector<torch::Tensor> rope_fwd(torch::Tensor q, torch::Tensor k,
                                     bool inverse) {
   TORCH_CHECK(q.is_cuda() && q.dim() == 4);
   TORCH_CHECK(rope_layout_ok(q), "rope: unsupported q layout");
-  TORCH_CHECK(k.sizes() == q.sizes() && k.strides() == q.strides(),
-              "rope: k must share q's layout");
+  // k may carry fewer heads than q (grouped-query attention): same B, S and
+  // hd, a valid layout of its own — the kernel is launched per tensor
+  TORCH_CHECK(k.is_cuda() && k.dim() == 4 && k.scalar_type() == q.scalar_type(),
+              "rope: k must be a 4-d tensor of q's dtype and device");
+  TORCH_CHECK(k.size(0) == q.size(0) && k.size(2) == q.size(2) && k.size(3) == q.size(3),
+              "rope: q and k must agree on batch, sequence and head_dim");
+  TORCH_CHECK(rope_layout_ok(k), "rope: unsupported k layout");
   TORCH_CHECK(cos_t.scalar_type() == torch::kFloat32 && cos_t.is_contiguous());
   TORCH_CHECK(cos_t.size(0) >= q.size(2), "rope cache shorter than sequence");
   auto qo = torch::empty_strided(q.sizes(), q.strides(), q.options());

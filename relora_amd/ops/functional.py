@@ -161,7 +161,8 @@ def build_rope_cache(rot_dim, seq_len, base=10000.0, device=None):
 
 
 def rope_torch(q, k, cos, sin, position_ids=None):
-    """q,k: [B, nh, S, hd]; cos/sin: [S_cache, rot_dim] fp32.
+    """q: [B, nh, S, hd], k: [B, nkv, S, hd] (nkv may be smaller than nh:
+    grouped-query attention); cos/sin: [S_cache, rot_dim] fp32.
 
     Rotates the first rot_dim features, passes the rest through.
     """
@@ -187,9 +188,12 @@ class _HipRoPE(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, cos, sin):
         # the kernel reads BHSD-contiguous AND transposed-BSHD views directly
-        # (same stride support as attention — no copies on the q/k path)
-        if not (_attn_layout_ok(q) and q.stride() == k.stride()):
-            q, k = q.contiguous(), k.contiguous()
+        # (same stride support as attention — no copies on the q/k path);
+        # it runs once per tensor, so k may have fewer heads and its own layout
+        if not _attn_layout_ok(q):
+            q = q.contiguous()
+        if not _attn_layout_ok(k):
+            k = k.contiguous()
         # Kernel contract: fp32 contiguous tables (a model .to(bf16) casts
         # registered buffers; converting [S,hd] back is noise next to the GEMMs).
         cos = cos.float().contiguous()
@@ -201,8 +205,10 @@ class _HipRoPE(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dqo, dko):
         cos, sin = ctx.saved_tensors
-        if not (_attn_layout_ok(dqo) and dqo.stride() == dko.stride()):
-            dqo, dko = dqo.contiguous(), dko.contiguous()
+        if not _attn_layout_ok(dqo):
+            dqo = dqo.contiguous()
+        if not _attn_layout_ok(dko):
+            dko = dko.contiguous()
         dq, dk = hip.ext().rope_fwd(dqo, dko, cos, sin, True)
         return dq, dk, None, None
 
@@ -276,8 +282,19 @@ def gelu(x):
 # ---------------------------------------------------------------------------
 
 
-def sdpa_torch(q, k, v, causal=True, dropout_p=0.0):
-    return F.scaled_dot_product_attention(q, k, v, dropout_p=dropout_p, is_causal=causal)
+def sdpa_torch(q, k, v, causal=True, dropout_p=0.0, scale=None):
+    """SDPA with the HIP path's head mapping: with fewer kv heads than query
+    heads, query head h reads kv head h // n_rep (HF `repeat_kv`).  The
+    expansion is a `repeat_interleave` on the head axis, so autograd sums
+    dK/dV back over each group and returns them as [B, nkv, S, hd]."""
+    nh, nkv = q.shape[1], k.shape[1]
+    if nkv != nh:
+        if nh % nkv != 0:
+            raise ValueError(f"kv heads ({nkv}) must divide query heads ({nh})")
+        k = k.repeat_interleave(nh // nkv, dim=1)
+        v = v.repeat_interleave(nh // nkv, dim=1)
+    return F.scaled_dot_product_attention(
+        q, k, v, dropout_p=dropout_p, is_causal=causal, scale=scale)
 
 
 def _attn_layout_ok(t):
@@ -292,11 +309,22 @@ def _attn_layout_ok(t):
             or s == (S * nh * hd, hd, nh * hd, 1))
 
 
+def _same_layout(a, b):
+    """equal shapes, and equal strides wherever a stride addresses anything
+    (a size-1 dim's stride is arbitrary)"""
+    return a.shape == b.shape and all(
+        sa == sb for n, sa, sb in zip(a.shape, a.stride(), b.stride()) if n > 1)
+
+
 class _HipFlashAttention(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, scale):
-        if not (_attn_layout_ok(q) and q.stride() == k.stride() == v.stride()):
-            q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        # q has its own stride triple, k/v share a second one ([B, nkv, S, hd],
+        # nkv dividing nh): copy only the side whose layout the kernels can't read
+        if not _attn_layout_ok(q):
+            q = q.contiguous()
+        if not (_attn_layout_ok(k) and _attn_layout_ok(v) and _same_layout(k, v)):
+            k, v = k.contiguous(), v.contiguous()
         o, lse = hip.ext().attn_fwd(q, k, v, scale)
         ctx.save_for_backward(q, k, v, o, lse)
         ctx.scale = scale
@@ -324,15 +352,22 @@ def _attn_hip_supported(q):
 
 
 def flash_attention(q, k, v, causal=True, dropout_p=0.0, scale=None):
-    """q,k,v: [B, nh, S, hd] -> [B, nh, S, hd]."""
+    """q: [B, nh, S, hd]; k, v: [B, nkv, S_kv, hd] with nkv dividing nh
+    (grouped-query attention: query head h reads kv head h // (nh // nkv))
+    -> [B, nh, S, hd]."""
     if scale is None:
         scale = q.shape[-1] ** -0.5
+    if k.shape != v.shape:
+        raise ValueError(f"k and v must have one shape, got {tuple(k.shape)} "
+                         f"and {tuple(v.shape)}")
+    if k.shape[1] < 1 or q.shape[1] % k.shape[1] != 0:
+        raise ValueError(f"kv heads ({k.shape[1]}) must divide query heads "
+                         f"({q.shape[1]})")
     if (causal and dropout_p == 0.0 and _attn_hip_supported(q)
+            and k.dtype == q.dtype and v.dtype == q.dtype
             and hip.use_hip(q, "attention")):
         return _HipFlashAttention.apply(q, k, v, scale)
-    return F.scaled_dot_product_attention(
-        q, k, v, dropout_p=dropout_p, is_causal=causal, scale=scale
-    )
+    return sdpa_torch(q, k, v, causal=causal, dropout_p=dropout_p, scale=scale)
 
 
 # ---------------------------------------------------------------------------

@@ -19,6 +19,27 @@ def _bytes_per_dtype(dtype):
     return torch.tensor([], dtype=dtype).element_size()
 
 
+def _kv_width(cfg):
+    """Output width of k_proj / v_proj: nkv * head_dim (== H for multi-head)."""
+    nh = cfg.num_attention_heads
+    nkv = getattr(cfg, "num_key_value_heads", None) or nh
+    return nkv * (cfg.hidden_size // nh)
+
+
+def estimate_param_count(cfg, lora_r=0):
+    """(model parameters, LoRA parameters) of a LLaMA-shaped config."""
+    H = cfg.hidden_size
+    L = cfg.num_hidden_layers
+    I = cfg.intermediate_size
+    V = cfg.vocab_size
+    KV = _kv_width(cfg)
+    # per layer: q and o are H x H, k and v are H x KV
+    n_params = V * H * 2 + L * (2 * H * H + 2 * H * KV + 3 * H * I + 2 * H) + H
+    lora_params = (L * lora_r * (2 * (H + H) + 2 * (H + KV) + 2 * (H + I) + (I + H))
+                   if lora_r else 0)
+    return n_params, lora_params
+
+
 def estimate_step_bytes(cfg, micro_batch, seq_len, dtype=torch.bfloat16,
                         trainable_ratio=1.0, lora_r=0):
     """Rough peak bytes for one training step at the given micro-batch."""
@@ -28,21 +49,22 @@ def estimate_step_bytes(cfg, micro_batch, seq_len, dtype=torch.bfloat16,
     I = cfg.intermediate_size
     V = cfg.vocab_size
     nh = cfg.num_attention_heads
+    KV = _kv_width(cfg)
     T = micro_batch * seq_len
 
-    n_params = V * H * 2 + L * (4 * H * H + 3 * H * I + 2 * H) + H
-    lora_params = L * lora_r * (4 * (H + H) + 2 * (H + I) + (I + H)) if lora_r else 0
+    n_params, lora_params = estimate_param_count(cfg, lora_r)
     weights = (n_params + lora_params) * e
     # grads + two Adam states for the trainable set
     n_train = int(n_params * trainable_ratio) + lora_params
     opt = n_train * e * 3
 
     # activations saved for backward, per layer:
-    #  norms in/out (2H), qkv+rope (3H), attention out (H), o-in (H),
-    #  mlp gate/up/act (2I + I), down-in (I) ≈ 7H + 4I per token
-    act_layer = T * (7 * H + 4 * I) * e
-    # attention saves q,k,v,o + lse
-    act_attn = T * (4 * H) * e + T * nh * 4
+    #  norms in/out (2H), qkv+rope (H + 2KV), attention out (H), o-in (H),
+    #  mlp gate/up/act (2I + I), down-in (I) ≈ 5H + 2KV + 4I per token
+    #  (KV = nkv * head_dim; 7H + 4I for multi-head)
+    act_layer = T * (5 * H + 2 * KV + 4 * I) * e
+    # attention saves q,o (H each), k,v (KV each) + lse
+    act_attn = T * (2 * H + 2 * KV) * e + T * nh * 4
     acts = L * (act_layer + act_attn)
     # logits path: bf16 logits + grad (chunked CE still peaks at one chunk)
     ce = 2 * min(T, 16384) * V * e

@@ -2,6 +2,7 @@
 flagship shape, plus optional SDPA comparison.
 
   python tools/bench_attention.py [--B 8] [--nh 32] [--S 2048] [--hd 64]
+  python tools/bench_attention.py --nkv 8 --per-kernel   # grouped-query, per-kernel us
   rocprofv3 --pmc SQ_WAVE_CYCLES,SQ_WAIT_ANY,SQ_WAIT_INST_ANY,SQ_LDS_BANK_CONFLICT \
       -d out -- python tools/bench_attention.py --iters 3 --what fwd
 """
@@ -27,6 +28,10 @@ def main():
     p = argparse.ArgumentParser()
     p.add_argument("--B", type=int, default=8)
     p.add_argument("--nh", type=int, default=32)
+    p.add_argument("--nkv", type=int, default=None,
+                   help="kv heads (grouped-query attention); default nh")
+    p.add_argument("--per-kernel", dest="per_kernel", action="store_true",
+                   help="also print the mean device time of each attention kernel")
     p.add_argument("--S", type=int, default=2048)
     p.add_argument("--hd", type=int, default=64)
     p.add_argument("--iters", type=int, default=30)
@@ -37,8 +42,9 @@ def main():
     torch.manual_seed(0)
     B, nh, S, hd = args.B, args.nh, args.S, args.hd
     q = torch.randn(B, nh, S, hd, device="cuda", dtype=torch.bfloat16)
-    k = torch.randn_like(q)
-    v = torch.randn_like(q)
+    nkv = args.nkv or nh
+    k = torch.randn(B, nkv, S, hd, device="cuda", dtype=torch.bfloat16)
+    v = torch.randn_like(k)
     do = torch.randn_like(q)
     scale = hd ** -0.5
     ext = hip.ext()
@@ -63,7 +69,25 @@ def main():
         t = timeit(lambda: ext.attn_bwd(q, k, v, o, lse, do, scale), args.iters)
         # bwd: dQ (2 GEMMs) + dKdV (4 GEMMs) + delta
         print(f"bwd : {t*1e3:8.3f} ms  {ff*2.5/t/1e12:7.1f} TF/s")
+    if args.per_kernel:
+        from torch.profiler import ProfilerActivity, profile
+
+        o, lse = ext.attn_fwd(q, k, v, scale)
+        torch.cuda.synchronize()
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            for _ in range(args.iters):
+                o, lse = ext.attn_fwd(q, k, v, scale)
+                ext.attn_bwd(q, k, v, o, lse, do, scale)
+            torch.cuda.synchronize()
+        for ev in prof.key_averages():
+            if "attn_" in ev.key:
+                name = ev.key.split("(")[0].replace("void ", "")
+                print(f"kernel {name}: {ev.device_time_total / ev.count:9.1f} us "
+                      f"x{ev.count}")
     if args.what == "sdpa":
+        if nkv != nh:
+            k = k.repeat_interleave(nh // nkv, dim=1)
+            v = v.repeat_interleave(nh // nkv, dim=1)
         def sdpa():
             return torch.nn.functional.scaled_dot_product_attention(
                 q, k, v, is_causal=True, scale=scale)
