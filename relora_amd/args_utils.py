@@ -5,12 +5,31 @@ our offline extension); batch-size algebra; token budget → steps; fp16
 forbidden; exactly-one optimizer-reset mode; `--relora` implies
 `--use_peft`; `--skip_batches` CSV → set."""
 
+import json
 import os
 import sys
 
 import yaml
 
 from relora_amd.utils.logging import logger
+
+
+def _is_pythia_run(args):
+    """does --model_config / --model_name_or_path name a Pythia (GPT-NeoX)
+    model?  Decided from the config's own model_type / architectures, with
+    the file name as the fallback for a config that cannot be read."""
+    path = args.model_config or args.model_name_or_path
+    if path is None:
+        return False
+    cfg_path = os.path.join(path, "config.json") if os.path.isdir(path) else path
+    try:
+        with open(cfg_path) as f:
+            cfg = json.load(f)
+        kind = " ".join([str(cfg.get("model_type", ""))] + list(cfg.get("architectures") or []))
+    except (OSError, ValueError):
+        kind = os.path.basename(str(path))
+    kind = kind.lower()
+    return "neox" in kind or "pythia" in kind
 
 
 def check_args_torchrun_main(args, n_cli_args=None):
@@ -96,6 +115,12 @@ def check_args_torchrun_main(args, n_cli_args=None):
 
     assert 0 <= args.optimizer_random_pruning < 1, "--optimizer_random_pruning must be between 0 and 1"
     assert 0 <= args.optimizer_magnitude_pruning < 1, "--optimizer_magnitude_pruning must be between 0 and 1"
+
+    if getattr(args, "intra_doc_masking", False) and _is_pythia_run(args):
+        raise ValueError(
+            "--intra_doc_masking is implemented for the LLaMA models only; "
+            "Pythia attends across document boundaries"
+        )
 
     if args.distributed_type == "fsdp":
         raise NotImplementedError(

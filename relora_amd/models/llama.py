@@ -121,8 +121,11 @@ class LlamaAttention(nn.Module):
         position_ids: Optional[torch.LongTensor] = None,
         past_key_value: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
         use_cache: bool = False,
+        doc_start: Optional[torch.Tensor] = None,
     ):
         bsz, q_len, _ = hidden_states.size()
+        if doc_start is not None and past_key_value is not None:
+            raise ValueError("doc_start cannot be combined with a kv cache")
         q, k, v = lora_group_forward(hidden_states, (self.q_proj, self.k_proj, self.v_proj))
         q = q.view(bsz, q_len, self.num_heads, self.head_dim).transpose(1, 2)
         k = k.view(bsz, q_len, self.num_key_value_heads, self.head_dim).transpose(1, 2)
@@ -146,7 +149,14 @@ class LlamaAttention(nn.Module):
         # parity with the reference: attention is ALWAYS causal in training;
         # padding masks are ignored (reference modeling_llama.py:221-224).
         # q_len==1 (cached decode) must not be top-left-aligned causal.
-        attn = ops.flash_attention(q, k, v, causal=q_len > 1)
+        # doc_start (int32 [B, S]) keeps every token inside its own document of
+        # a packed row; RoPE positions are NOT reset at document starts (the
+        # scores depend only on i - j, so a document's outputs do not depend
+        # on where it sits in the row)
+        if doc_start is not None:
+            attn = ops.flash_attention(q, k, v, causal=True, doc_start=doc_start)
+        else:
+            attn = ops.flash_attention(q, k, v, causal=q_len > 1)
         attn = attn.transpose(1, 2).reshape(bsz, q_len, self.hidden_size)
         return self.o_proj(attn), present
 
@@ -160,7 +170,8 @@ class LlamaDecoderLayer(nn.Module):
         self.post_attention_layernorm = LlamaRMSNorm(config.hidden_size, eps=config.rms_norm_eps)
 
     def forward(self, hidden_states, position_ids=None, past_key_value=None,
-                use_cache=False, pending_residual=None, defer_add=False):
+                use_cache=False, pending_residual=None, defer_add=False,
+                doc_start=None):
         """Residual adds fuse into the norms (K16, same bf16 rounding as the
         unfused composition).  With `defer_add`, the MLP add is handed to
         the NEXT layer's input norm (or the final norm) as
@@ -177,6 +188,7 @@ class LlamaDecoderLayer(nn.Module):
         attn_out, present = self.self_attn(
             normed, position_ids=position_ids,
             past_key_value=past_key_value, use_cache=use_cache,
+            doc_start=doc_start,
         )
         normed2, residual2 = ops.add_rmsnorm(
             attn_out, residual, self.post_attention_layernorm.weight,
@@ -239,7 +251,10 @@ class LlamaModel(LlamaPreTrainedModel):
         output_attentions=False,
         output_hidden_states=False,
         return_dict=True,
+        doc_start=None,  # int32 [B, S] intra-document mask (ops.flash_attention)
     ):
+        if doc_start is not None and past_key_values is not None:
+            raise ValueError("doc_start cannot be combined with past_key_values")
         if inputs_embeds is None:
             inputs_embeds = self.embed_tokens(input_ids)
         hidden_states = inputs_embeds
@@ -264,13 +279,14 @@ class LlamaModel(LlamaPreTrainedModel):
             if self.gradient_checkpointing and self.training:
                 hidden_states, pending, present = torch.utils.checkpoint.checkpoint(
                     layer, hidden_states, position_ids, past, False,
-                    pending, defer, use_reentrant=False,
+                    pending, defer, doc_start, use_reentrant=False,
                 )
             else:
                 hidden_states, pending, present = layer(
                     hidden_states, position_ids=position_ids,
                     past_key_value=past, use_cache=use_cache,
                     pending_residual=pending, defer_add=defer,
+                    doc_start=doc_start,
                 )
             if use_cache:
                 next_cache.append(present)
@@ -331,6 +347,7 @@ class LlamaForCausalLM(LlamaPreTrainedModel, GenerationMixin):
         output_attentions=False,
         output_hidden_states=False,
         return_dict=True,
+        doc_start=None,
     ):
         outputs = self.model(
             input_ids=input_ids,
@@ -341,6 +358,7 @@ class LlamaForCausalLM(LlamaPreTrainedModel, GenerationMixin):
             use_cache=use_cache,
             output_hidden_states=output_hidden_states,
             return_dict=True,
+            doc_start=doc_start,
         )
         hidden_states = outputs.last_hidden_state
 
@@ -422,6 +440,7 @@ class LlamaForSequenceClassification(LlamaPreTrainedModel):
         output_attentions=False,
         output_hidden_states=False,
         return_dict=True,
+        doc_start=None,
     ):
         outputs = self.model(
             input_ids=input_ids,
@@ -431,6 +450,7 @@ class LlamaForSequenceClassification(LlamaPreTrainedModel):
             inputs_embeds=inputs_embeds,
             use_cache=use_cache,
             return_dict=True,
+            doc_start=doc_start,
         )
         hidden_states = outputs.last_hidden_state
         logits = self.score(hidden_states)

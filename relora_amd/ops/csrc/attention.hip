@@ -506,12 +506,48 @@ DEV_INLINE bf16x8 pack_p_frag(const float* p16, int g) {
 #define LOG2E 1.44269504088896340736f
 #define DEFER_MAX_THR 11.5f  // log2 domain ~ e^8 (guide T13; bf16 accum headroom)
 
-template <int HD, int MINW = 2, bool TRR = false, bool GQA = false>
+// ---------------------------------------------------------------------------
+// Intra-document masking (template flag DOC on the three v3 kernels that
+// serve padded head dim <= 64).  doc_start is int32 [B, S]: doc_start[b, i]
+// is the index of the first token of the document token i belongs to, and
+// query i attends to kv j iff doc_start[b, i] <= j <= i.  A well-formed
+// doc_start is non-decreasing along S with doc_start[i] <= i, so every row
+// keeps its diagonal (no empty row: lse stays finite, no 0/0 in the
+// backward), and over any run of rows the smallest value is the first
+// row's and the largest the last row's.
+//
+// doc_start values only ever enter comparisons and clamped loop bounds,
+// never an address: arbitrary int32 content can give meaningless numbers
+// but no access out of bounds.  Nothing is validated on the host (that
+// would synchronise).
+//
+// doc_bounds (forward and dQ, q lane-local): `ds` is the lane's own value
+// (0 for rows at or past S), `ds_lo`/`ds_hi` those of the wave's first and
+// last valid row (wave-uniform loads), and `kt0` the first kv tile any row
+// of the block can see, clamped into [0, n_tiles-1].  `dsp` points at batch
+// row b; every index below is clamped into [0, S-1].
+// ---------------------------------------------------------------------------
+DEV_INLINE void doc_bounds(const int* __restrict__ dsp, int S, int q_start, int w_first,
+                           int q_abs, int n_tiles, int& ds, int& ds_lo, int& ds_hi,
+                           int& kt0) {
+  ds = (q_abs < S) ? dsp[q_abs] : 0;
+  ds_lo = ds_hi = 0;
+  if (w_first < S) {
+    ds_lo = __builtin_amdgcn_readfirstlane(dsp[w_first]);
+    ds_hi = __builtin_amdgcn_readfirstlane(dsp[min(w_first + 31, S - 1)]);
+  }
+  // q_start < S by the launch grid; min() keeps the read in bounds regardless
+  const int ds_blk = __builtin_amdgcn_readfirstlane(dsp[min(q_start, S - 1)]);
+  kt0 = min(max(ds_blk / TILE, 0), n_tiles - 1);
+}
+
+template <int HD, int MINW = 2, bool TRR = false, bool GQA = false, bool DOC = false>
 __global__ __launch_bounds__(512, MINW) void attn_fwd_v3_kernel(
     const __hip_bfloat16* __restrict__ q, const __hip_bfloat16* __restrict__ k,
     const __hip_bfloat16* __restrict__ v, __hip_bfloat16* __restrict__ out,
     float* __restrict__ lse, int S, int hd, int nh, long bst, long hst, int ld,
-    long bst_kv, long hst_kv, int ld_kv, int n_rep, float scale) {
+    long bst_kv, long hst_kv, int ld_kv, int n_rep, float scale,
+    const int* __restrict__ doc_start) {
   constexpr int KSTEPS = HD / 16;  // QK^T k-steps per 32-kv subtile
   constexpr int NT32 = HD / 32;    // O^T 32-row hd tiles
   constexpr int LDK = HD + LPAD;
@@ -554,19 +590,29 @@ __global__ __launch_bounds__(512, MINW) void attn_fwd_v3_kernel(
   const int n_tiles = (q_max_abs / TILE) + 1;
   const float sc2 = scale * LOG2E;
 
+  // DOC: ds is this lane's doc_start (0 for rows past S), ds_lo/ds_hi the
+  // wave's first and last valid row's (wave-uniform), kt0 the first kv tile
+  // the block needs (see doc_bounds)
+  int ds = 0, ds_lo = 0, ds_hi = 0, kt0 = 0;
+  if constexpr (DOC)
+    doc_bounds(doc_start + (long)(bh / nh) * S, S, q_start, q_start + wave * 32, q_abs,
+               n_tiles, ds, ds_lo, ds_hi, kt0);
+
+  // the tile loop runs kt0 .. n_tiles-1 and the double-buffer parity stays
+  // on kt, so the prologue stages tile kt0 into buffer kt0 & 1
   bf16x8 rk[NV], rv[NV];
-  tile_load_regs<HD, NV>(rk, kp, 0, S, hd, ldk);
-  tile_load_regs<HD, NV>(rv, vp, 0, S, hd, ldk);
-  if (TRR) tile_write_tr<HD, NV>(lds_vt, rv);
-  else tile_write_t<HD, NV>(lds_vt, rv);
-  tile_write_rows<HD, NV>(lds_k, rk, LDK);
-  if (n_tiles > 1) {
-    tile_load_regs<HD, NV>(rk, kp, TILE, S, hd, ldk);
-    tile_load_regs<HD, NV>(rv, vp, TILE, S, hd, ldk);
+  tile_load_regs<HD, NV>(rk, kp, kt0 * TILE, S, hd, ldk);
+  tile_load_regs<HD, NV>(rv, vp, kt0 * TILE, S, hd, ldk);
+  if (TRR) tile_write_tr<HD, NV>(lds_vt + (kt0 & 1) * HD * TILE, rv);
+  else tile_write_t<HD, NV>(lds_vt + (kt0 & 1) * HD * TILE, rv);
+  tile_write_rows<HD, NV>(lds_k + (kt0 & 1) * TILE * LDK, rk, LDK);
+  if (kt0 + 1 < n_tiles) {
+    tile_load_regs<HD, NV>(rk, kp, (kt0 + 1) * TILE, S, hd, ldk);
+    tile_load_regs<HD, NV>(rv, vp, (kt0 + 1) * TILE, S, hd, ldk);
   }
   __syncthreads();
 
-  for (int kt = 0; kt < n_tiles; ++kt) {
+  for (int kt = kt0; kt < n_tiles; ++kt) {
     const int cur = kt & 1;
     const int kv0 = kt * TILE;
     const __bf16* kb = lds_k + cur * TILE * LDK;
@@ -578,11 +624,19 @@ __global__ __launch_bounds__(512, MINW) void attn_fwd_v3_kernel(
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
       const int kv0s = kv0 + 32 * t;
-      // wave-uniform edge: the wave's lowest q row decides the masked path
-      const bool edge = (kv0s + 31 > q_start + wave * 32) || (kv0s + 32 > S);
+      // wave-uniform edge: the wave's lowest q row decides the masked path;
+      // DOC: so does its last valid row's doc_start, the wave's largest
+      const bool edge = (kv0s + 31 > q_start + wave * 32) || (kv0s + 32 > S) ||
+                        (DOC && kv0s < ds_hi);
       if (kv0s > q_max_abs) break;  // fully-masked subtile (block-uniform)
+      // DOC: a subtile wholly below the wave's smallest doc_start contributes
+      // nothing to any of its rows.  The wave skips the MFMA/softmax work of
+      // that subtile and nothing else: the staging below and the barrier that
+      // ends the tile are executed by every wave of the block.
+      const bool skip = DOC && (kv0s + 31 < ds_lo);
 
       float p_val[16];
+      if (!skip) {
       __builtin_amdgcn_s_setprio(1);
       {
         f32x16 acc = (f32x16)(0.f);
@@ -594,7 +648,8 @@ __global__ __launch_bounds__(512, MINW) void attn_fwd_v3_kernel(
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             const int kv_abs = kv0s + (r & 3) + 8 * (r >> 2) + 4 * hi;
-            p_val[r] = (kv_abs > q_abs || kv_abs >= S) ? -INFINITY : acc[r] * sc2;
+            p_val[r] = (kv_abs > q_abs || kv_abs >= S || (DOC && kv_abs < ds))
+                           ? -INFINITY : acc[r] * sc2;
           }
         } else {
 #pragma unroll
@@ -602,6 +657,7 @@ __global__ __launch_bounds__(512, MINW) void attn_fwd_v3_kernel(
         }
       }
       __builtin_amdgcn_s_setprio(0);
+      }
 
       // stage tile kt+1 between the two MFMA clusters (T14 split)
       if (t == 0 && kt + 1 < n_tiles) {
@@ -613,8 +669,14 @@ __global__ __launch_bounds__(512, MINW) void attn_fwd_v3_kernel(
           tile_load_regs<HD, NV>(rv, vp, (kt + 2) * TILE, S, hd, ldk);
         }
       }
+      if (skip) continue;
 
-      // online softmax, fully per-lane (q = lane&31)
+      // online softmax, fully per-lane (q = lane&31).  A row whose scores so
+      // far are all masked (its first subtile lies above the diagonal of a
+      // partial block, or, DOC, below its own doc_start while the wave's
+      // smallest is lower) has m_tile == m2 == -inf: the guards below give
+      // alpha = 0 and p = 0, so l_run and o_acc stay 0 until its first
+      // unmasked score arrives
       float m_tile = p_val[0];
 #pragma unroll
       for (int i = 1; i < 16; ++i) m_tile = fmaxf(m_tile, p_val[i]);
@@ -747,14 +809,15 @@ DEV_INLINE f32x4 load_f32x4_guard(const float* p, long idx, long n) {
   return r;
 }
 
-template <int HD, int NWAVE = 8, int MINW = 2, bool GQA = false>
+template <int HD, int NWAVE = 8, int MINW = 2, bool GQA = false, bool DOC = false>
 // NWAVE*32 q rows per block; MINW=4 caps VGPRs at 128 (occ experiment)
 __global__ __launch_bounds__(NWAVE * 64, MINW) void attn_bwd_dq_v3_kernel(
     const __hip_bfloat16* __restrict__ q, const __hip_bfloat16* __restrict__ k,
     const __hip_bfloat16* __restrict__ v, const __hip_bfloat16* __restrict__ dout,
     const float* __restrict__ lse, const float* __restrict__ delta,
     __hip_bfloat16* __restrict__ dq, int S, int hd, int nh, long bst, long hst,
-    int ld, long bst_kv, long hst_kv, int ld_kv, int n_rep, float scale) {
+    int ld, long bst_kv, long hst_kv, int ld_kv, int n_rep, float scale,
+    const int* __restrict__ doc_start) {
   constexpr int KSTEPS = HD / 16;
   constexpr int NT32 = HD / 32;
   constexpr int LDK = HD + LPAD;
@@ -802,19 +865,25 @@ __global__ __launch_bounds__(NWAVE * 64, MINW) void attn_bwd_dq_v3_kernel(
   const int q_max_abs = min(q_start + QROWS - 1, S - 1);
   const int n_tiles = (q_max_abs / TILE) + 1;
 
+  // DOC: same bounds, loop start and skipping rule as the v3 forward
+  int ds = 0, ds_lo = 0, ds_hi = 0, kt0 = 0;
+  if constexpr (DOC)
+    doc_bounds(doc_start + (long)(bh / nh) * S, S, q_start, q_start + wave * 32, q_abs,
+               n_tiles, ds, ds_lo, ds_hi, kt0);
+
   bf16x8 rk[NV], rv[NV];
-  tile_load_regs<HD, NV, NT>(rk, kp, 0, S, hd, ldk);
-  tile_load_regs<HD, NV, NT>(rv, vp, 0, S, hd, ldk);
-  tile_write_rows<HD, NV, NT>(lds_k, rk, LDK);
-  tile_write_rows<HD, NV, NT>(lds_v, rv, LDK);
-  tile_write_t<HD, NV, NT>(lds_kt, rk);
-  if (n_tiles > 1) {
-    tile_load_regs<HD, NV, NT>(rk, kp, TILE, S, hd, ldk);
-    tile_load_regs<HD, NV, NT>(rv, vp, TILE, S, hd, ldk);
+  tile_load_regs<HD, NV, NT>(rk, kp, kt0 * TILE, S, hd, ldk);
+  tile_load_regs<HD, NV, NT>(rv, vp, kt0 * TILE, S, hd, ldk);
+  tile_write_rows<HD, NV, NT>(lds_k + (kt0 & 1) * TILE * LDK, rk, LDK);
+  tile_write_rows<HD, NV, NT>(lds_v + (kt0 & 1) * TILE * LDK, rv, LDK);
+  tile_write_t<HD, NV, NT>(lds_kt + (kt0 & 1) * HD * TILE, rk);
+  if (kt0 + 1 < n_tiles) {
+    tile_load_regs<HD, NV, NT>(rk, kp, (kt0 + 1) * TILE, S, hd, ldk);
+    tile_load_regs<HD, NV, NT>(rv, vp, (kt0 + 1) * TILE, S, hd, ldk);
   }
   __syncthreads();
 
-  for (int kt = 0; kt < n_tiles; ++kt) {
+  for (int kt = kt0; kt < n_tiles; ++kt) {
     const int cur = kt & 1;
     const int kv0 = kt * TILE;
     const __bf16* kb = lds_k + cur * TILE * LDK;
@@ -825,10 +894,14 @@ __global__ __launch_bounds__(NWAVE * 64, MINW) void attn_bwd_dq_v3_kernel(
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
       const int kv0s = kv0 + 32 * t;
-      const bool edge_t = (kv0s + 31 > q_start + wave * 32) || (kv0s + 32 > S);
+      const bool edge_t = (kv0s + 31 > q_start + wave * 32) || (kv0s + 32 > S) ||
+                          (DOC && kv0s < ds_hi);
       if (kv0s > q_max_abs) break;
+      // DOC: only this wave's MFMA work is skipped, never staging or barrier
+      const bool skip = DOC && (kv0s + 31 < ds_lo);
 
       float ds_val[16];
+      if (!skip) {
       __builtin_amdgcn_s_setprio(1);
       {
         f32x16 sa = (f32x16)(0.f), dpa = (f32x16)(0.f);
@@ -845,7 +918,7 @@ __global__ __launch_bounds__(NWAVE * 64, MINW) void attn_bwd_dq_v3_kernel(
           float p;
           if (edge_t) {
             const int kv_abs = kv0s + (r & 3) + 8 * (r >> 2) + 4 * hi;
-            p = (kv_abs <= q_abs && kv_abs < S && q_abs < S)
+            p = (kv_abs <= q_abs && kv_abs < S && q_abs < S && !(DOC && kv_abs < ds))
                     ? exp2f(sa[r] * sc2 - lse2) : 0.f;
           } else {
             p = exp2f(sa[r] * sc2 - lse2);
@@ -854,6 +927,7 @@ __global__ __launch_bounds__(NWAVE * 64, MINW) void attn_bwd_dq_v3_kernel(
         }
       }
       __builtin_amdgcn_s_setprio(0);
+      }
 
       if (t == 0 && kt + 1 < n_tiles) {
         tile_write_rows<HD, NV, NT>(lds_k + (cur ^ 1) * TILE * LDK, rk, LDK);
@@ -864,6 +938,7 @@ __global__ __launch_bounds__(NWAVE * 64, MINW) void attn_bwd_dq_v3_kernel(
           tile_load_regs<HD, NV, NT>(rv, vp, (kt + 2) * TILE, S, hd, ldk);
         }
       }
+      if (skip) continue;
 
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -896,15 +971,16 @@ __global__ __launch_bounds__(NWAVE * 64, MINW) void attn_bwd_dq_v3_kernel(
   }
 }
 
-template <int HD, bool TRR = false, bool GQA = false>
-// HD <= 64; TRR: tr-read Q^T/dO^T images
+template <int HD, bool TRR = false, bool GQA = false, bool DOC = false>
+// HD <= 64; TRR: tr-read Q^T/dO^T images; DOC: intra-document masking (see
+// doc_bounds for the representation and the out-of-bounds argument)
 __global__ __launch_bounds__(512) void attn_bwd_dkdv_v3_kernel(
     const __hip_bfloat16* __restrict__ q, const __hip_bfloat16* __restrict__ k,
     const __hip_bfloat16* __restrict__ v, const __hip_bfloat16* __restrict__ dout,
     const float* __restrict__ lse, const float* __restrict__ delta,
     __hip_bfloat16* __restrict__ dk, __hip_bfloat16* __restrict__ dv,
     int S, int hd, int nh, long bst, long hst, int ld, long bst_kv, long hst_kv,
-    int ld_kv, int n_rep, float scale) {
+    int ld_kv, int n_rep, float scale, const int* __restrict__ doc_start) {
   constexpr int KSTEPS = HD / 16;
   constexpr int NT32 = HD / 32;
   constexpr int LDK = HD + LPAD;
@@ -955,6 +1031,31 @@ __global__ __launch_bounds__(512) void attn_bwd_dkdv_v3_kernel(
   const int first_qt = kv_start / TILE;
   const int n_q_tiles = (S + TILE - 1) / TILE;
 
+  // DOC: the q-tile loop ends, block-uniformly, at the first q tile whose
+  // first row's doc_start lies past the block's last kv row — by
+  // monotonicity every later tile is fully masked too.  The bound does not
+  // depend on the head, so it is found once: each lane tests one tile
+  // (every index < S since qt < n_q_tiles), a ballot picks the first.  All
+  // waves read the same values and agree.  q_end replaces n_q_tiles in the
+  // loop AND in every staging/prefetch condition below, so the two-stage
+  // Q/dO pipeline and the per-tile and per-head barriers run exactly as in
+  // a full loop over a sequence of q_end tiles.
+  int q_end = n_q_tiles;
+  const int* dsp = nullptr;
+  if constexpr (DOC) {
+    dsp = doc_start + (long)bi * S;
+    const int kv_last = min(kv_start + 255, S - 1);
+    for (int c0 = first_qt + 1; c0 < n_q_tiles; c0 += 64) {
+      const int qt_l = c0 + lane;
+      const bool past = qt_l < n_q_tiles && dsp[(long)qt_l * TILE] > kv_last;
+      const unsigned long long m = __ballot(past);
+      if (m) {
+        q_end = c0 + __ffsll(m) - 1;
+        break;
+      }
+    }
+  }
+
   bf16x8 rq[NV], rdo[NV];
   const int reps = GQA ? n_rep : 1;
   for (int rep = 0; rep < reps; ++rep) {
@@ -981,13 +1082,13 @@ __global__ __launch_bounds__(512) void attn_bwd_dkdv_v3_kernel(
       tile_write_t<HD, NV>(lds_qt, rq);
       tile_write_t<HD, NV>(lds_dot, rdo);
     }
-    if (first_qt + 1 < n_q_tiles) {
+    if (first_qt + 1 < q_end) {
       tile_load_regs<HD, NV>(rq, qp, (first_qt + 1) * TILE, S, hd, ld);
       tile_load_regs<HD, NV>(rdo, dop, (first_qt + 1) * TILE, S, hd, ld);
     }
     __syncthreads();
 
-    for (int qt = first_qt; qt < n_q_tiles; ++qt) {
+    for (int qt = first_qt; qt < q_end; ++qt) {
       const int cur = qt & 1;
       const int q0 = qt * TILE;
       const __bf16* qb = lds_q + cur * TILE * LDK;
@@ -1000,7 +1101,12 @@ __global__ __launch_bounds__(512) void attn_bwd_dkdv_v3_kernel(
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
         const int q0s = q0 + 32 * t;
-        const bool edge_t = (q0s < kv_start + 255) || (q0s + 32 > S);
+        bool edge_t = (q0s < kv_start + 255) || (q0s + 32 > S);
+        // DOC: the subtile's largest doc_start is its last valid row's; the
+        // masked path is needed when it passes this wave's first kv row
+        if constexpr (DOC)
+          edge_t = edge_t || __builtin_amdgcn_readfirstlane(dsp[min(q0s + 31, S - 1)]) >
+                                 kv_start + wave * 32;
 
         float pt_val[16], dst_val[16];
         __builtin_amdgcn_s_setprio(1);
@@ -1020,6 +1126,23 @@ __global__ __launch_bounds__(512) void attn_bwd_dkdv_v3_kernel(
             const long qrow = q0s + 8 * qd + 4 * hi;
             const f32x4 lse4 = load_f32x4_guard(lsep, qrow, S);
             const f32x4 dl4 = load_f32x4_guard(deltap, qrow, S);
+            // DOC: doc_start of the quad's q rows.  The quad's address depends
+            // on the lane only through `hi`, so both candidates are loaded
+            // wave-uniformly (index clamped into [0, S-1]; rows at or past S
+            // are masked below anyway) and selected per lane — a per-lane
+            // int4 next to lse4/dl4 pushed the hd64 kernel past 256 VGPRs
+            // into scratch
+            int dsq[4] = {0, 0, 0, 0};
+            if constexpr (DOC) {
+#pragma unroll
+              for (int i = 0; i < 4; ++i) {
+                const int a =
+                    __builtin_amdgcn_readfirstlane(dsp[min(q0s + 8 * qd + i, S - 1)]);
+                const int b =
+                    __builtin_amdgcn_readfirstlane(dsp[min(q0s + 8 * qd + 4 + i, S - 1)]);
+                dsq[i] = hi ? b : a;
+              }
+            }
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
               const int r = 4 * qd + i;
@@ -1027,7 +1150,8 @@ __global__ __launch_bounds__(512) void attn_bwd_dkdv_v3_kernel(
               float p;
               if (edge_t) {
                 const int q_abs_r = q0s + (r & 3) + 8 * (r >> 2) + 4 * hi;
-                p = (q_abs_r >= kv_abs && q_abs_r < S && kv_abs < S)
+                p = (q_abs_r >= kv_abs && q_abs_r < S && kv_abs < S &&
+                     !(DOC && kv_abs < dsq[i]))
                         ? exp2f(sa[r] * sc2 - lse2) : 0.f;
               } else {
                 p = exp2f(sa[r] * sc2 - lse2);
@@ -1039,7 +1163,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dkdv_v3_kernel(
         }
         __builtin_amdgcn_s_setprio(0);
 
-        if (t == 0 && qt + 1 < n_q_tiles) {
+        if (t == 0 && qt + 1 < q_end) {
           tile_write_rows<HD, NV>(lds_q + (cur ^ 1) * TILE * LDK, rq, LDK);
           tile_write_rows<HD, NV>(lds_do + (cur ^ 1) * TILE * LDK, rdo, LDK);
           if (TRR) {
@@ -1049,7 +1173,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dkdv_v3_kernel(
             tile_write_t<HD, NV>(lds_qt + (cur ^ 1) * HD * TILE, rq);
             tile_write_t<HD, NV>(lds_dot + (cur ^ 1) * HD * TILE, rdo);
           }
-          if (qt + 2 < n_q_tiles) {
+          if (qt + 2 < q_end) {
             tile_load_regs<HD, NV>(rq, qp, (qt + 2) * TILE, S, hd, ld);
             tile_load_regs<HD, NV>(rdo, dop, (qt + 2) * TILE, S, hd, ld);
           }
@@ -1546,12 +1670,35 @@ static void with_gqa(bool gqa, F&& f) {
   else f(std::false_type{});
 }
 
+// Intra-document masking: doc_start is int32, contiguous, [B, S], on q's
+// device.  Its content is not validated (that would synchronise): the
+// kernels only compare against it and clamp what they derive from it.
+// Only the three default v3 instantiations for padded head dim <= 64 have a
+// DOC path; flash_attention routes larger head dims to masked SDPA.
+static const int* doc_start_ptr(const c10::optional<torch::Tensor>& doc_start,
+                                const torch::Tensor& q, const torch::Tensor& k) {
+  if (!doc_start.has_value()) return nullptr;
+  const torch::Tensor& d = *doc_start;
+  TORCH_CHECK(d.scalar_type() == torch::kInt32, "attention: doc_start must be int32");
+  TORCH_CHECK(d.device() == q.device(), "attention: doc_start must be on q's device");
+  TORCH_CHECK(d.dim() == 2 && d.size(0) == q.size(0) && d.size(1) == q.size(2),
+              "attention: doc_start must be [B, S] = [", q.size(0), ", ", q.size(2),
+              "], got ", d.sizes());
+  TORCH_CHECK(d.is_contiguous(), "attention: doc_start must be contiguous");
+  TORCH_CHECK(k.size(2) == q.size(2), "attention: doc_start needs S_q == S_kv");
+  TORCH_CHECK(pad32((int)q.size(3)) <= 64,
+              "attention: doc_start is supported for padded head_dim <= 64, got head_dim ",
+              q.size(3));
+  return d.data_ptr<int>();
+}
+
 #define BF(t) ((const __hip_bfloat16*)(t).data_ptr())
 #define GEOM_ARGS g.bst, g.hst, g.ld, g.bst_kv, g.hst_kv, g.ld_kv, g.n_rep, (float)scale
 
 std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor v,
-                                    double scale) {
+                                    double scale, c10::optional<torch::Tensor> doc_start) {
   const AttnGeom g = attn_geometry(q, k, v);
+  const int* dsp = doc_start_ptr(doc_start, q, k);
   const int B = q.size(0), nh = q.size(1), S = q.size(2), hd = q.size(3);
   const int HDP = pad32(hd);
   auto out = torch::empty_strided(q.sizes(), q.strides(), q.options());
@@ -1559,7 +1706,24 @@ std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k, torch::Ten
   auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
   dim3 block(512);
 #define FWD_ARGS BF(q), BF(k), BF(v), (__hip_bfloat16*)out.data_ptr(), \
-                 lse.data_ptr<float>(), S, hd, nh, GEOM_ARGS
+                 lse.data_ptr<float>(), S, hd, nh, GEOM_ARGS, dsp
+  if (dsp) {
+    // the doc path ignores RELORA_AMD_ATTN_FWD / OCC4 / TR_FWD: always the
+    // default instantiation (MINW=4, TRR), kv-strided code (handles
+    // n_rep == 1 and every layout pair)
+    dim3 grid((S + 255) / 256, B * nh);
+    if (HDP == 32) {
+      size_t smem = (2 * TILE * (32 + LPAD) + 2 * 32 * TILE) * sizeof(__bf16);
+      hipLaunchKernelGGL((attn_fwd_v3_kernel<32, 4, true, true, true>), grid, block, smem,
+                         stream, FWD_ARGS);
+    } else {
+      size_t smem = (2 * TILE * (64 + LPAD) + 2 * 64 * TILE) * sizeof(__bf16);
+      hipLaunchKernelGGL((attn_fwd_v3_kernel<64, 4, true, true, true>), grid, block, smem,
+                         stream, FWD_ARGS);
+    }
+    HIP_CHECK_LAST();
+    return {out, lse};
+  }
   if (attn_fwd_version() == 3) {
     DISPATCH_HD(HDP, {
       dim3 grid((S + 255) / 256, B * nh);
@@ -1596,7 +1760,8 @@ std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k, torch::Ten
     size_t smem = (2 * TILE * LDK + 2 * HD * TILE + RF * 8 * 16 * LDP) * sizeof(__bf16);
     with_gqa(g.gqa, [&](auto G) {
       hipLaunchKernelGGL((attn_fwd_kernel<HD, decltype(G)::value>), grid, block, smem,
-                         stream, FWD_ARGS);
+                         stream, BF(q), BF(k), BF(v), (__hip_bfloat16*)out.data_ptr(),
+                         lse.data_ptr<float>(), S, hd, nh, GEOM_ARGS);
     });
   });
 #undef FWD_ARGS
@@ -1606,8 +1771,9 @@ std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k, torch::Ten
 
 std::vector<torch::Tensor> attn_bwd(torch::Tensor q, torch::Tensor k, torch::Tensor v,
                                     torch::Tensor o, torch::Tensor lse, torch::Tensor dout,
-                                    double scale) {
+                                    double scale, c10::optional<torch::Tensor> doc_start) {
   const AttnGeom g = attn_geometry(q, k, v);
+  const int* dsp = doc_start_ptr(doc_start, q, k);
   const int B = q.size(0), nh = q.size(1), S = q.size(2), hd = q.size(3);
   const int nkv = k.size(1);
   const int HDP = pad32(hd);
@@ -1651,6 +1817,33 @@ std::vector<torch::Tensor> attn_bwd(torch::Tensor q, torch::Tensor k, torch::Ten
   // over the n_rep query heads of its group
   const int dkdv_gy = g.gqa ? B * nkv : B * nh;
   dim3 block(512);
+  if (dsp) {
+    // the doc path ignores RELORA_AMD_ATTN_BWD / DQ_4WAVE / DQ_OCC4 /
+    // TR_DKDV: always the default instantiations, kv-strided code, so the
+    // dK/dV grid is one block row per (b, kv head)
+    const dim3 grid_dq((S + 255) / 256, B * nh), grid_dkdv((S + 255) / 256, B * nkv);
+    if (HDP == 32) {
+      constexpr int HD = 32, LDK = HD + LPAD;
+      hipLaunchKernelGGL((attn_bwd_dq_v3_kernel<HD, 8, 2, true, true>), grid_dq, block,
+                         (2 * TILE * LDK * 2 + 2 * HD * TILE) * sizeof(__bf16), stream,
+                         DQ_ARGS, dsp);
+      HIP_CHECK_LAST();
+      hipLaunchKernelGGL((attn_bwd_dkdv_v3_kernel<HD, false, true, true>), grid_dkdv, block,
+                         (2 * TILE * LDK * 2 + 2 * HD * TILE * 2) * sizeof(__bf16), stream,
+                         DKDV_ARGS, dsp);
+    } else {
+      constexpr int HD = 64, LDK = HD + LPAD;
+      hipLaunchKernelGGL((attn_bwd_dq_v3_kernel<HD, 8, 2, true, true>), grid_dq, block,
+                         (2 * TILE * LDK * 2 + 2 * HD * TILE) * sizeof(__bf16), stream,
+                         DQ_ARGS, dsp);
+      HIP_CHECK_LAST();
+      hipLaunchKernelGGL((attn_bwd_dkdv_v3_kernel<HD, false, true, true>), grid_dkdv, block,
+                         (2 * TILE * LDK * 2 + 2 * HD * TILE * 2) * sizeof(__bf16), stream,
+                         DKDV_ARGS, dsp);
+    }
+    HIP_CHECK_LAST();
+    return {dq, dk, dv};
+  }
   DISPATCH_HD(HDP, {
     const int LDK = HD + LPAD, LDT = TILE + LPAD;
     if (bwd_ver == 3 && HD <= 96) {  // dq v3 at hd128 hits the VGPR cap
@@ -1668,13 +1861,13 @@ std::vector<torch::Tensor> attn_bwd(torch::Tensor q, torch::Tensor k, torch::Ten
         constexpr bool GQA = decltype(G)::value;
         if (dqocc4 && HD <= 64)
           hipLaunchKernelGGL((attn_bwd_dq_v3_kernel<HD, 8, 4, GQA>),
-                             dim3((S + 255) / 256, B * nh), block, smem_dq3, stream, DQ_ARGS);
+                             dim3((S + 255) / 256, B * nh), block, smem_dq3, stream, DQ_ARGS, dsp);
         else if (dq4w && HD <= 64)
           hipLaunchKernelGGL((attn_bwd_dq_v3_kernel<HD, 4, 2, GQA>),
-                             dim3((S + 127) / 128, B * nh), dim3(256), smem_dq3, stream, DQ_ARGS);
+                             dim3((S + 127) / 128, B * nh), dim3(256), smem_dq3, stream, DQ_ARGS, dsp);
         else
           hipLaunchKernelGGL((attn_bwd_dq_v3_kernel<HD, 8, 2, GQA>),
-                             dim3((S + 255) / 256, B * nh), block, smem_dq3, stream, DQ_ARGS);
+                             dim3((S + 255) / 256, B * nh), block, smem_dq3, stream, DQ_ARGS, dsp);
       });
       HIP_CHECK_LAST();
     } else {
@@ -1699,11 +1892,11 @@ std::vector<torch::Tensor> attn_bwd(torch::Tensor q, torch::Tensor k, torch::Ten
         if (trr)
           hipLaunchKernelGGL((attn_bwd_dkdv_v3_kernel<HD, true, GQA>),
                              dim3((S + 255) / 256, dkdv_gy), block, smem_dkdv3, stream,
-                             DKDV_ARGS);
+                             DKDV_ARGS, dsp);
         else
           hipLaunchKernelGGL((attn_bwd_dkdv_v3_kernel<HD, false, GQA>),
                              dim3((S + 255) / 256, dkdv_gy), block, smem_dkdv3, stream,
-                             DKDV_ARGS);
+                             DKDV_ARGS, dsp);
       });
       HIP_CHECK_LAST();
     } else {

@@ -79,10 +79,10 @@ std::vector<torch::Tensor> quantize_int8(torch::Tensor x);
 torch::Tensor dequantize_int8(torch::Tensor q, torch::Tensor absmax, long n, torch::ScalarType dtype);
 // attention.hip
 std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor v,
-                                    double scale);
+                                    double scale, c10::optional<torch::Tensor> doc_start);
 std::vector<torch::Tensor> attn_bwd(torch::Tensor q, torch::Tensor k, torch::Tensor v,
                                     torch::Tensor o, torch::Tensor lse, torch::Tensor dout,
-                                    double scale);
+                                    double scale, c10::optional<torch::Tensor> doc_start);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rmsnorm_fwd", &rmsnorm_fwd, "RMSNorm forward (gfx950)");
@@ -126,6 +126,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dequantize_nf4", &dequantize_nf4, "NF4 blockwise dequantize (gfx950)");
   m.def("quantize_int8", &quantize_int8, "int8 blockwise quantize (gfx950)");
   m.def("dequantize_int8", &dequantize_int8, "int8 blockwise dequantize (gfx950)");
-  m.def("attn_fwd", &attn_fwd, "causal flash attention forward (gfx950 MFMA)");
-  m.def("attn_bwd", &attn_bwd, "causal flash attention backward (gfx950 MFMA)");
+  // doc_start: optional int32 [B, S] intra-document mask (padded head_dim <= 64)
+  m.def("attn_fwd", &attn_fwd, "causal flash attention forward (gfx950 MFMA)",
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("scale"),
+        py::arg("doc_start") = py::none());
+  m.def("attn_bwd", &attn_bwd, "causal flash attention backward (gfx950 MFMA)",
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"), py::arg("lse"),
+        py::arg("dout"), py::arg("scale"), py::arg("doc_start") = py::none());
 }

@@ -282,19 +282,63 @@ def gelu(x):
 # ---------------------------------------------------------------------------
 
 
-def sdpa_torch(q, k, v, causal=True, dropout_p=0.0, scale=None):
+def doc_starts_from_eos(input_ids, eos_token_id):
+    """int32 [B, S]: for every token the index of the first token of its
+    document, the `doc_start` of `flash_attention`.  The token after an
+    `eos` starts a new document (the `eos` belongs to the document it ends)
+    and position 0 always starts one.  Compare / where / cummax only: works
+    on CPU and GPU and never synchronises."""
+    S = input_ids.shape[-1]
+    pos = torch.arange(S, device=input_ids.device).expand_as(input_ids)
+    starts = torch.zeros_like(input_ids, dtype=torch.bool)
+    starts[..., 1:] = input_ids[..., :-1] == eos_token_id
+    starts[..., 0] = True
+    marked = torch.where(starts, pos, torch.zeros_like(pos))
+    return marked.cummax(dim=-1).values.to(torch.int32)
+
+
+def doc_mask(doc_start, S):
+    """bool [B, 1, S, S], True where query i may attend to kv j:
+    doc_start[b, i] <= j <= i."""
+    pos = torch.arange(S, device=doc_start.device)
+    i, j = pos[:, None], pos[None, :]
+    return ((j <= i) & (j >= doc_start[:, :, None].long())).unsqueeze(1)
+
+
+def sdpa_torch(q, k, v, causal=True, dropout_p=0.0, scale=None, doc_start=None):
     """SDPA with the HIP path's head mapping: with fewer kv heads than query
     heads, query head h reads kv head h // n_rep (HF `repeat_kv`).  The
     expansion is a `repeat_interleave` on the head axis, so autograd sums
-    dK/dV back over each group and returns them as [B, nkv, S, hd]."""
+    dK/dV back over each group and returns them as [B, nkv, S, hd].
+
+    With `doc_start` (int32 [B, S], see `flash_attention`) the causal mask is
+    replaced by the boolean intra-document mask `doc_mask`."""
     nh, nkv = q.shape[1], k.shape[1]
     if nkv != nh:
         if nh % nkv != 0:
             raise ValueError(f"kv heads ({nkv}) must divide query heads ({nh})")
         k = k.repeat_interleave(nh // nkv, dim=1)
         v = v.repeat_interleave(nh // nkv, dim=1)
+    if doc_start is not None:
+        _check_doc_start(q, k, causal, doc_start)
+        return F.scaled_dot_product_attention(
+            q, k, v, attn_mask=doc_mask(doc_start, q.shape[-2]), dropout_p=dropout_p,
+            scale=scale)
     return F.scaled_dot_product_attention(
         q, k, v, dropout_p=dropout_p, is_causal=causal, scale=scale)
+
+
+def _check_doc_start(q, k, causal, doc_start):
+    if not causal:
+        raise ValueError("doc_start requires causal=True")
+    if q.shape[-2] != k.shape[-2]:
+        raise ValueError(f"doc_start requires equal q and kv lengths, got "
+                         f"{q.shape[-2]} and {k.shape[-2]}")
+    if tuple(doc_start.shape) != (q.shape[0], q.shape[-2]):
+        raise ValueError(f"doc_start must be [B, S] = [{q.shape[0]}, {q.shape[-2]}], "
+                         f"got {tuple(doc_start.shape)}")
+    if doc_start.dtype != torch.int32:
+        raise ValueError(f"doc_start must be int32, got {doc_start.dtype}")
 
 
 def _attn_layout_ok(t):
@@ -318,24 +362,29 @@ def _same_layout(a, b):
 
 class _HipFlashAttention(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, scale):
+    def forward(ctx, q, k, v, scale, doc_start=None):
         # q has its own stride triple, k/v share a second one ([B, nkv, S, hd],
         # nkv dividing nh): copy only the side whose layout the kernels can't read
         if not _attn_layout_ok(q):
             q = q.contiguous()
         if not (_attn_layout_ok(k) and _attn_layout_ok(v) and _same_layout(k, v)):
             k, v = k.contiguous(), v.contiguous()
-        o, lse = hip.ext().attn_fwd(q, k, v, scale)
-        ctx.save_for_backward(q, k, v, o, lse)
+        if doc_start is None:
+            o, lse = hip.ext().attn_fwd(q, k, v, scale)
+            ctx.save_for_backward(q, k, v, o, lse)
+        else:
+            doc_start = doc_start.contiguous()
+            o, lse = hip.ext().attn_fwd(q, k, v, scale, doc_start)
+            ctx.save_for_backward(q, k, v, o, lse, doc_start)
         ctx.scale = scale
         return o
 
     @staticmethod
     def backward(ctx, do):
-        q, k, v, o, lse = ctx.saved_tensors
+        q, k, v, o, lse, *doc = ctx.saved_tensors
         # the host copies `do` into q's layout only if it differs
-        dq, dk, dv = hip.ext().attn_bwd(q, k, v, o, lse, do, ctx.scale)
-        return dq, dk, dv, None
+        dq, dk, dv = hip.ext().attn_bwd(q, k, v, o, lse, do, ctx.scale, *doc)
+        return dq, dk, dv, None, None
 
 
 def _attn_hip_supported(q):
@@ -351,10 +400,23 @@ def _attn_hip_supported(q):
     return q.dtype == torch.bfloat16 and hd <= 128 and hd % 8 == 0
 
 
-def flash_attention(q, k, v, causal=True, dropout_p=0.0, scale=None):
+def _pad32(hd):
+    return (hd + 31) // 32 * 32
+
+
+def flash_attention(q, k, v, causal=True, dropout_p=0.0, scale=None, doc_start=None):
     """q: [B, nh, S, hd]; k, v: [B, nkv, S_kv, hd] with nkv dividing nh
     (grouped-query attention: query head h reads kv head h // (nh // nkv))
-    -> [B, nh, S, hd]."""
+    -> [B, nh, S, hd].
+
+    `doc_start` (int32 [B, S] on q's device, the same for all heads) turns on
+    intra-document masking for packed rows: doc_start[b, i] is the index of
+    the first token of the document token i belongs to, and query i attends
+    to kv j iff doc_start[b, i] <= j <= i (`doc_starts_from_eos` builds it).
+    It needs causal=True and S == S_kv.  The HIP kernels take it where they
+    take the plain call AND the head dim pads to <= 64 (shipped head dims 32,
+    48, 64); everything else (80, 128, 52, fp32, CPU) runs SDPA with the
+    boolean mask."""
     if scale is None:
         scale = q.shape[-1] ** -0.5
     if k.shape != v.shape:
@@ -363,11 +425,17 @@ def flash_attention(q, k, v, causal=True, dropout_p=0.0, scale=None):
     if k.shape[1] < 1 or q.shape[1] % k.shape[1] != 0:
         raise ValueError(f"kv heads ({k.shape[1]}) must divide query heads "
                          f"({q.shape[1]})")
+    if doc_start is not None:
+        _check_doc_start(q, k, causal, doc_start)
     if (causal and dropout_p == 0.0 and _attn_hip_supported(q)
             and k.dtype == q.dtype and v.dtype == q.dtype
             and hip.use_hip(q, "attention")):
-        return _HipFlashAttention.apply(q, k, v, scale)
-    return sdpa_torch(q, k, v, causal=causal, dropout_p=dropout_p, scale=scale)
+        if doc_start is None:
+            return _HipFlashAttention.apply(q, k, v, scale)
+        if _pad32(q.shape[-1]) <= 64:
+            return _HipFlashAttention.apply(q, k, v, scale, doc_start)
+    return sdpa_torch(q, k, v, causal=causal, dropout_p=dropout_p, scale=scale,
+                      doc_start=doc_start)
 
 
 # ---------------------------------------------------------------------------

@@ -31,7 +31,7 @@ import torch.distributed as dist
 import torch.utils.data
 import yaml
 
-from relora_amd import args_utils, training_utils
+from relora_amd import args_utils, ops, training_utils
 from relora_amd.data.dataloader import SkipDataLoader, SyntheticDataset
 from relora_amd.models import build_model_from_config, load_model_config
 from relora_amd.models.llama import LlamaForCausalLM
@@ -87,6 +87,12 @@ def parse_args(args=None):
     parser.add_argument("--synthetic_data", default=None, type=lambda x: x.lower() == "true" or None,
                         help="Train on deterministic random tokens (offline benchmarking)")
     parser.add_argument("--max_length", type=int, default=512)
+    parser.add_argument("--intra_doc_masking", default=False, type=lambda x: x.lower() == "true",
+                        help="Packed rows: keep attention inside each document (LLaMA only). "
+                             "Off by default; the reference attends across document boundaries.")
+    parser.add_argument("--doc_separator_id", type=int, default=None,
+                        help="Token that ends a document for --intra_doc_masking. Default: the "
+                             "tokenizer's eos_token_id, else the model config's.")
 
     parser.add_argument("--batch_size", type=_int_or_auto, default=None,
                         help="micro-batch per GPU, or 'auto' to size for the device HBM (288 GB on MI355X)")
@@ -147,8 +153,26 @@ def parse_args(args=None):
     return args
 
 
+def resolve_doc_separator_id(args, tokenizer, model_config):
+    """The token id that ends a document for --intra_doc_masking: the flag's
+    own value, else the tokenizer's eos_token_id where the trainer has a
+    tokenizer, else the model config's."""
+    sep = args.doc_separator_id
+    if sep is None and tokenizer is not None:
+        sep = getattr(tokenizer, "eos_token_id", None)
+        if sep is None:
+            sep = getattr(tokenizer, "eod", None)  # Megatron-style tokenizers
+    if sep is None:
+        sep = getattr(model_config, "eos_token_id", None)
+    if sep is None:
+        raise ValueError("--intra_doc_masking needs --doc_separator_id: neither the tokenizer "
+                         "nor the model config has an eos_token_id")
+    return int(sep)
+
+
 @torch.no_grad()
-def evaluate_model(model, eval_dataloader, device, target_eval_tokens=10_000_000):
+def evaluate_model(model, eval_dataloader, device, target_eval_tokens=10_000_000,
+                   doc_separator_id=None):
     _time = time.time()
     was_training = model.training
     model.eval()
@@ -167,6 +191,8 @@ def evaluate_model(model, eval_dataloader, device, target_eval_tokens=10_000_000
         if target_eval_tokens != -1 and i > n_eval_iters:
             break
         batch = {k: v.to(device) for k, v in batch.items()}
+        if doc_separator_id is not None:
+            batch["doc_start"] = ops.doc_starts_from_eos(batch["input_ids"], doc_separator_id)
         loss = model(**batch, labels=batch["input_ids"]).loss
         ddp_loss_info[0] += loss.detach()
         ddp_loss_info[1] += 1
@@ -445,6 +471,14 @@ def main(args):
                 torch.load(state_path, map_location="cpu", weights_only=True), strict=True
             )
 
+    # intra-document masking: doc_start is derived from every batch's
+    # input_ids (training and evaluation alike); loss masking is unchanged
+    doc_separator_id = None
+    if args.intra_doc_masking:
+        doc_separator_id = resolve_doc_separator_id(args, tokenizer, model_config)
+        logger.info(f"Intra-document attention masking is ON; documents end at token id "
+                    f"{doc_separator_id}")
+
     if args.synthetic_data:
         n_train = max(args.total_batch_size * (args.num_training_steps + 1), args.total_batch_size)
         train_dataset = SyntheticDataset(model_config.vocab_size, args.max_length,
@@ -701,6 +735,8 @@ def main(args):
         is_boundary = global_step % args.gradient_accumulation == 0
         model.set_gradient_sync(is_boundary)  # reduce only at accumulation boundary
 
+        if doc_separator_id is not None:
+            batch["doc_start"] = ops.doc_starts_from_eos(batch["input_ids"], doc_separator_id)
         loss = model(**batch, labels=batch["input_ids"]).loss
 
         loss_info[0] += loss.detach()
@@ -763,7 +799,8 @@ def main(args):
                 training_utils.delete_old_checkpoints(args.save_dir, keep=args.keep_checkpoints)
 
         if update_step % args.eval_every == 0:
-            total_loss, evaluated_on_tokens = evaluate_model(model, eval_loader, device)
+            total_loss, evaluated_on_tokens = evaluate_model(
+                model, eval_loader, device, doc_separator_id=doc_separator_id)
             if global_rank == 0:
                 wandb.log({"final_eval_loss": float(total_loss),
                            "final_eval_tokens": evaluated_on_tokens}, step=global_step)
@@ -865,7 +902,8 @@ def main(args):
     if use_gpu:
         torch.cuda.empty_cache()
     total_loss, evaluated_on_tokens = evaluate_model(
-        model, eval_loader, device, target_eval_tokens=100_000_000
+        model, eval_loader, device, target_eval_tokens=100_000_000,
+        doc_separator_id=doc_separator_id
     )
     if global_rank == 0:
         wandb.log({"final_eval_loss": float(total_loss),
@@ -874,7 +912,8 @@ def main(args):
 
     if test_loader is not None:
         total_loss, evaluated_on_tokens = evaluate_model(
-            model, test_loader, device, target_eval_tokens=-1
+            model, test_loader, device, target_eval_tokens=-1,
+            doc_separator_id=doc_separator_id
         )
         if global_rank == 0:
             wandb.log({"final_test_loss": float(total_loss),

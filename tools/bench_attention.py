@@ -3,6 +3,8 @@ flagship shape, plus optional SDPA comparison.
 
   python tools/bench_attention.py [--B 8] [--nh 32] [--S 2048] [--hd 64]
   python tools/bench_attention.py --nkv 8 --per-kernel   # grouped-query, per-kernel us
+  python tools/bench_attention.py --doc-len 512          # intra-document masking, uniform
+                                                         # documents (0: all-zero doc_start)
   rocprofv3 --pmc SQ_WAVE_CYCLES,SQ_WAIT_ANY,SQ_WAIT_INST_ANY,SQ_LDS_BANK_CONFLICT \
       -d out -- python tools/bench_attention.py --iters 3 --what fwd
 """
@@ -37,6 +39,10 @@ def main():
     p.add_argument("--iters", type=int, default=30)
     p.add_argument("--warmup", type=int, default=5)
     p.add_argument("--what", choices=["fwd", "bwd", "both", "sdpa"], default="both")
+    p.add_argument("--doc-len", dest="doc_len", type=int, default=None,
+                   help="run the doc_start path with uniform documents of this length "
+                        "(0: one document per row, i.e. the overhead of the flag); "
+                        "TF/s stay those of the full causal triangle")
     args = p.parse_args()
 
     torch.manual_seed(0)
@@ -48,6 +54,11 @@ def main():
     do = torch.randn_like(q)
     scale = hd ** -0.5
     ext = hip.ext()
+    doc = ()
+    if args.doc_len is not None:
+        pos = torch.arange(S, device="cuda", dtype=torch.int32)
+        ds = pos - pos % args.doc_len if args.doc_len > 0 else torch.zeros_like(pos)
+        doc = (ds.expand(B, S).contiguous(),)
 
     def timeit(fn, iters):
         for _ in range(args.warmup):
@@ -61,23 +72,23 @@ def main():
 
     ff = flops_fwd(B, nh, S, hd)
     if args.what in ("fwd", "both"):
-        o, lse = ext.attn_fwd(q, k, v, scale)
-        t = timeit(lambda: ext.attn_fwd(q, k, v, scale), args.iters)
+        o, lse = ext.attn_fwd(q, k, v, scale, *doc)
+        t = timeit(lambda: ext.attn_fwd(q, k, v, scale, *doc), args.iters)
         print(f"fwd : {t*1e3:8.3f} ms  {ff/t/1e12:7.1f} TF/s")
     if args.what in ("bwd", "both"):
-        o, lse = ext.attn_fwd(q, k, v, scale)
-        t = timeit(lambda: ext.attn_bwd(q, k, v, o, lse, do, scale), args.iters)
+        o, lse = ext.attn_fwd(q, k, v, scale, *doc)
+        t = timeit(lambda: ext.attn_bwd(q, k, v, o, lse, do, scale, *doc), args.iters)
         # bwd: dQ (2 GEMMs) + dKdV (4 GEMMs) + delta
         print(f"bwd : {t*1e3:8.3f} ms  {ff*2.5/t/1e12:7.1f} TF/s")
     if args.per_kernel:
         from torch.profiler import ProfilerActivity, profile
 
-        o, lse = ext.attn_fwd(q, k, v, scale)
+        o, lse = ext.attn_fwd(q, k, v, scale, *doc)
         torch.cuda.synchronize()
         with profile(activities=[ProfilerActivity.CUDA]) as prof:
             for _ in range(args.iters):
-                o, lse = ext.attn_fwd(q, k, v, scale)
-                ext.attn_bwd(q, k, v, o, lse, do, scale)
+                o, lse = ext.attn_fwd(q, k, v, scale, *doc)
+                ext.attn_bwd(q, k, v, o, lse, do, scale, *doc)
             torch.cuda.synchronize()
         for ev in prof.key_averages():
             if "attn_" in ev.key:
