@@ -116,6 +116,14 @@ def check_args_torchrun_main(args, n_cli_args=None):
     assert 0 <= args.optimizer_random_pruning < 1, "--optimizer_random_pruning must be between 0 and 1"
     assert 0 <= args.optimizer_magnitude_pruning < 1, "--optimizer_magnitude_pruning must be between 0 and 1"
 
+    # YAML values arrive untyped ("1e-2" parses as a string)
+    args.z_loss = float(getattr(args, "z_loss", 0.0) or 0.0)
+    args.label_smoothing = float(getattr(args, "label_smoothing", 0.0) or 0.0)
+    if not args.z_loss >= 0:
+        raise ValueError(f"--z_loss must be >= 0, got {args.z_loss}")
+    if not 0 <= args.label_smoothing < 1:
+        raise ValueError(f"--label_smoothing must be in [0, 1), got {args.label_smoothing}")
+
     if getattr(args, "intra_doc_masking", False) and _is_pythia_run(args):
         raise ValueError(
             "--intra_doc_masking is implemented for the LLaMA models only; "

@@ -17,7 +17,6 @@ import torch.nn as nn
 import torch.utils.checkpoint
 from transformers.modeling_outputs import (
     BaseModelOutputWithPast,
-    CausalLMOutputWithPast,
     SequenceClassifierOutputWithPast,
 )
 from transformers.generation import GenerationMixin
@@ -25,6 +24,8 @@ from transformers.modeling_utils import PreTrainedModel
 
 from relora_amd import ops
 from relora_amd.models.config import LlamaConfig
+from relora_amd.models.loss import (
+    CausalLMLossOutput, LossOptionsMixin, fused_lm_loss, unfused_lm_loss)
 from relora_amd.relora import lora_group_forward
 
 
@@ -309,7 +310,7 @@ class LlamaModel(LlamaPreTrainedModel):
         )
 
 
-class LlamaForCausalLM(LlamaPreTrainedModel, GenerationMixin):
+class LlamaForCausalLM(LossOptionsMixin, LlamaPreTrainedModel, GenerationMixin):
     # honored only when config.tie_word_embeddings is True (the reference's
     # llama recipes keep the head untied — configs/llama_*.json)
     _tied_weights_keys = {"lm_head.weight": "model.embed_tokens.weight"}
@@ -364,6 +365,9 @@ class LlamaForCausalLM(LlamaPreTrainedModel, GenerationMixin):
 
         loss = None
         logits = None
+        ce_loss = z_loss = None
+        # runtime loss options apply to training only; eval is plain CE
+        z_coef, smoothing = self._active_loss_options()
         # lm_head weight may be a plain Parameter or a ReLoRA-wrapped Linear;
         # fused CE only handles the plain case (lm_head is never a LoRA target)
         if labels is not None and self.fused_ce and isinstance(self.lm_head, nn.Linear) \
@@ -371,25 +375,27 @@ class LlamaForCausalLM(LlamaPreTrainedModel, GenerationMixin):
             B, S, H = hidden_states.shape
             shift_hidden = hidden_states[:, :-1, :].reshape(-1, H)
             shift_labels = labels[:, 1:].reshape(-1).to(shift_hidden.device)
-            loss = ops.fused_cross_entropy(shift_hidden, self.lm_head.weight, shift_labels)
+            loss, ce_loss, z_loss = fused_lm_loss(
+                shift_hidden, self.lm_head.weight, shift_labels, z_coef, smoothing)
         else:
             logits = self.lm_head(hidden_states)
             if labels is not None:
                 shift_logits = logits[:, :-1, :].contiguous()
                 shift_labels = labels[:, 1:].contiguous().to(shift_logits.device)
-                loss = nn.functional.cross_entropy(
+                loss, ce_loss, z_loss = unfused_lm_loss(
                     shift_logits.view(-1, self.config.vocab_size),
-                    shift_labels.view(-1),
-                )
+                    shift_labels.view(-1), z_coef, smoothing)
 
         if not return_dict:
             out = (logits,) + (outputs.past_key_values,)
             return (loss,) + out if loss is not None else out
-        return CausalLMOutputWithPast(
+        return CausalLMLossOutput(
             loss=loss,
             logits=logits,
             past_key_values=outputs.past_key_values,
             hidden_states=outputs.hidden_states,
+            ce_loss=ce_loss,
+            z_loss=z_loss,
         )
 
     def prepare_inputs_for_generation(self, input_ids, past_key_values=None, **kwargs):

@@ -15,12 +15,14 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 import torch.utils.checkpoint
-from transformers.modeling_outputs import BaseModelOutputWithPast, CausalLMOutputWithPast
+from transformers.modeling_outputs import BaseModelOutputWithPast
 from transformers.generation import GenerationMixin
 from transformers.modeling_utils import PreTrainedModel
 
 from relora_amd import ops
 from relora_amd.models.config import GPTNeoXConfig
+from relora_amd.models.loss import (
+    CausalLMLossOutput, LossOptionsMixin, fused_lm_loss, unfused_lm_loss)
 
 
 class GPTNeoXRotary(nn.Module):
@@ -282,7 +284,7 @@ class GPTNeoXModel(GPTNeoXPreTrainedModel):
         )
 
 
-class GPTNeoXForCausalLM(GPTNeoXPreTrainedModel, GenerationMixin):
+class GPTNeoXForCausalLM(LossOptionsMixin, GPTNeoXPreTrainedModel, GenerationMixin):
     # dict form (target -> source) per the installed transformers' tying API
     _tied_weights_keys = {"embed_out.weight": "gpt_neox.embed_in.weight"}
 
@@ -332,29 +334,35 @@ class GPTNeoXForCausalLM(GPTNeoXPreTrainedModel, GenerationMixin):
 
         loss = None
         logits = None
+        ce_loss = z_loss = None
+        # runtime loss options apply to training only; eval is plain CE
+        z_coef, smoothing = self._active_loss_options()
         if labels is not None and self.fused_ce and isinstance(self.embed_out, nn.Linear) \
                 and self.embed_out.bias is None:
             B, S, H = hidden_states.shape
             shift_hidden = hidden_states[:, :-1, :].reshape(-1, H)
             shift_labels = labels[:, 1:].reshape(-1).to(shift_hidden.device)
-            loss = ops.fused_cross_entropy(shift_hidden, self.embed_out.weight, shift_labels)
+            loss, ce_loss, z_loss = fused_lm_loss(
+                shift_hidden, self.embed_out.weight, shift_labels, z_coef, smoothing)
         else:
             logits = self.embed_out(hidden_states)
             if labels is not None:
                 shift_logits = logits[:, :-1, :].contiguous()
                 shift_labels = labels[:, 1:].contiguous().to(shift_logits.device)
-                loss = F.cross_entropy(
-                    shift_logits.view(-1, self.config.vocab_size), shift_labels.view(-1)
-                )
+                loss, ce_loss, z_loss = unfused_lm_loss(
+                    shift_logits.view(-1, self.config.vocab_size),
+                    shift_labels.view(-1), z_coef, smoothing)
 
         if not return_dict:
             out = (logits, outputs.past_key_values)
             return (loss,) + out if loss is not None else out
-        return CausalLMOutputWithPast(
+        return CausalLMLossOutput(
             loss=loss,
             logits=logits,
             past_key_values=outputs.past_key_values,
             hidden_states=outputs.hidden_states,
+            ce_loss=ce_loss,
+            z_loss=z_loss,
         )
 
     def prepare_inputs_for_generation(self, input_ids, past_key_values=None, **kwargs):

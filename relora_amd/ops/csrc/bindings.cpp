@@ -30,6 +30,10 @@ std::vector<torch::Tensor> ce_row_stats(torch::Tensor logits, torch::Tensor labe
                                         long ignore_index);
 void ce_grad_(torch::Tensor logits, torch::Tensor labels, torch::Tensor lse,
               double gscale, long ignore_index);
+std::vector<torch::Tensor> ce_row_stats_ex(torch::Tensor logits, torch::Tensor labels,
+                                           long ignore_index);
+void ce_grad_ex_(torch::Tensor logits, torch::Tensor labels, torch::Tensor lse,
+                 double gscale, double z_loss, double label_smoothing, long ignore_index);
 // adamw.hip
 void fused_adamw(std::vector<torch::Tensor> params, std::vector<torch::Tensor> grads,
                  std::vector<torch::Tensor> exp_avgs, std::vector<torch::Tensor> exp_avg_sqs,
@@ -98,6 +102,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gelu_bwd", &gelu_bwd, "exact-erf GELU backward (gfx950)");
   m.def("ce_row_stats", &ce_row_stats, "CE row lse/target (gfx950)");
   m.def("ce_grad_", &ce_grad_, "CE in-place softmax-onehot grad (gfx950)");
+  m.def("ce_row_stats_ex", &ce_row_stats_ex, "CE row lse/target/row-sum (gfx950)");
+  m.def("ce_grad_ex_", &ce_grad_ex_,
+        "CE in-place grad with z-loss and label smoothing (gfx950)");
   m.def("fused_adamw", &fused_adamw, "multi-tensor AdamW step (gfx950)");
   m.def("multi_tensor_l2norm", &multi_tensor_l2norm, "multi-tensor L2 norm (gfx950)");
   m.def("multi_tensor_scale_", &multi_tensor_scale_, "multi-tensor scale (gfx950)");

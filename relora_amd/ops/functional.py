@@ -466,15 +466,38 @@ def _row_stats_torch(logits, labels, ignore_index):
     return lse, tgt
 
 
+def _row_stats_ex_torch(logits, labels, ignore_index):
+    lse, tgt = _row_stats_torch(logits, labels, ignore_index)
+    return lse, tgt, logits.float().sum(dim=-1)
+
+
+def _check_loss_options(z_loss, label_smoothing):
+    if not z_loss >= 0.0:
+        raise ValueError(f"z_loss must be >= 0, got {z_loss}")
+    if not 0.0 <= label_smoothing < 1.0:
+        raise ValueError(f"label_smoothing must be in [0, 1), got {label_smoothing}")
+
+
 class _FusedCrossEntropy(torch.autograd.Function):
-    """hidden [M,H], weight [V,H], labels [M] -> mean CE over labels != ignore."""
+    """hidden [M,H], weight [V,H], labels [M] -> mean CE over labels != ignore.
+
+    With z_loss (z) or label_smoothing (eps) non-zero the row objective is
+        lse - (1-eps)*x_t - (eps/V)*sum_j x_j + z*lse^2
+    and forward returns (loss, ce, zl): the objective plus the detached plain
+    cross-entropy mean(lse - x_t) and z*mean(lse^2).  With both at 0 it is the
+    plain kernel pair and a single output."""
 
     @staticmethod
-    def forward(ctx, hidden, weight, labels, ignore_index):
+    def forward(ctx, hidden, weight, labels, ignore_index, z_loss=0.0, label_smoothing=0.0):
         M = hidden.shape[0]
         device = hidden.device
+        ex = z_loss != 0.0 or label_smoothing != 0.0
         lse_all = torch.empty(M, dtype=torch.float32, device=device)
         loss_sum = torch.zeros((), dtype=torch.float32, device=device)
+        if ex:
+            V = weight.shape[0]
+            ce_sum = torch.zeros_like(loss_sum)
+            z_sum = torch.zeros_like(loss_sum)
         valid = labels != ignore_index
         n_valid = int(valid.sum().item())
         use_hip = hip.use_hip(hidden, "ce")
@@ -486,24 +509,49 @@ class _FusedCrossEntropy(torch.autograd.Function):
             if keep_logits:
                 saved_logits = logits
             lab = labels[s:e]
-            if use_hip:
-                lse, tgt = hip.ext().ce_row_stats(logits, lab, ignore_index)
-            else:
-                lse, tgt = _row_stats_torch(logits, lab, ignore_index)
-            lse_all[s:e] = lse
+            if not ex:
+                if use_hip:
+                    lse, tgt = hip.ext().ce_row_stats(logits, lab, ignore_index)
+                else:
+                    lse, tgt = _row_stats_torch(logits, lab, ignore_index)
+                lse_all[s:e] = lse
+                vmask = lab != ignore_index
+                loss_sum += torch.where(vmask, lse - tgt, torch.zeros_like(lse)).sum()
+                continue
             vmask = lab != ignore_index
-            loss_sum += torch.where(vmask, lse - tgt, torch.zeros_like(lse)).sum()
+            if use_hip:
+                lse, tgt, rsum = hip.ext().ce_row_stats_ex(logits, lab.contiguous(), ignore_index)
+            else:
+                lse, tgt, rsum = _row_stats_ex_torch(logits, lab, ignore_index)
+            lse_all[s:e] = lse
+            zero = torch.zeros_like(lse)
+            ce_c = torch.where(vmask, lse - tgt, zero).sum()
+            z_c = torch.where(vmask, lse * lse, zero).sum()
+            # eps * (x_t - mean_j x_j): what smoothing adds to lse - x_t
+            sm_c = torch.where(vmask, tgt - rsum / V, zero).sum()
+            ce_sum += ce_c
+            z_sum += z_c
+            loss_sum += ce_c + label_smoothing * sm_c + z_loss * z_c
         ctx.save_for_backward(hidden, weight, labels, lse_all,
                               saved_logits if saved_logits is not None
                               else hidden.new_empty(0))
         ctx.ignore_index = ignore_index
         ctx.n_valid = max(n_valid, 1)
-        return loss_sum / max(n_valid, 1)
+        ctx.z_loss = z_loss
+        ctx.label_smoothing = label_smoothing
+        if not ex:
+            return loss_sum / max(n_valid, 1)
+        ce = ce_sum / max(n_valid, 1)
+        zl = z_sum * (z_loss / max(n_valid, 1))
+        ctx.mark_non_differentiable(ce, zl)
+        return loss_sum / max(n_valid, 1), ce, zl
 
     @staticmethod
-    def backward(ctx, grad_out):
+    def backward(ctx, grad_out, *_parts):
         hidden, weight, labels, lse_all, saved_logits = ctx.saved_tensors
         ignore_index = ctx.ignore_index
+        z_loss, eps = ctx.z_loss, ctx.label_smoothing
+        ex = z_loss != 0.0 or eps != 0.0
         M, H = hidden.shape
         use_hip = hip.use_hip(hidden, "ce")
         dh = torch.empty_like(hidden)
@@ -521,14 +569,20 @@ class _FusedCrossEntropy(torch.autograd.Function):
             lse = lse_all[s:e]
             if use_hip:
                 # in-place: logits buffer becomes dlogits (same dtype)
-                hip.ext().ce_grad_(logits, lab, lse, gscale, ignore_index)
+                if ex:
+                    hip.ext().ce_grad_ex_(logits, lab.contiguous(), lse, gscale,
+                                          z_loss, eps, ignore_index)
+                else:
+                    hip.ext().ce_grad_(logits, lab, lse, gscale, ignore_index)
                 dlogits = logits
             else:
                 p = torch.exp(logits.float() - lse.unsqueeze(1))
                 vmask = (lab != ignore_index)
+                if ex:
+                    p = p * (1.0 + 2.0 * z_loss * lse).unsqueeze(1) - eps / logits.shape[1]
                 p[~vmask] = 0.0
                 safe = lab.clamp_min(0)
-                p[vmask, safe[vmask]] -= 1.0
+                p[vmask, safe[vmask]] -= 1.0 - eps
                 dlogits = (p * gscale).to(logits.dtype)
             dh[s:e] = dlogits @ weight
             if single_chunk:
@@ -537,15 +591,31 @@ class _FusedCrossEntropy(torch.autograd.Function):
                 dw_acc += (dlogits.t() @ hidden[s:e]).float()
         if not single_chunk:
             dw = dw_acc.to(weight.dtype)
-        return dh, dw, None, None
+        return dh, dw, None, None, None, None
 
 
-def fused_cross_entropy(hidden, weight, labels, ignore_index=-100):
+def fused_cross_entropy(hidden, weight, labels, ignore_index=-100, z_loss=0.0,
+                        label_smoothing=0.0, return_parts=False):
     """Mean cross-entropy of `hidden @ weight.T` against `labels`.
 
     hidden: [M, H] (already shifted/flattened); weight: [V, H]; labels: [M].
+
+    z_loss adds the PaLM auxiliary term `z_loss * mean(lse^2)`;
+    label_smoothing is `F.cross_entropy`'s argument of that name.  Both
+    default to 0, which is the plain kernel path.  return_parts=True returns
+    `(loss, ce, zl)`: the optimised objective plus, detached, the plain
+    cross-entropy (what perplexity is computed from) and the z-loss term.
     """
-    return _FusedCrossEntropy.apply(hidden, weight, labels, ignore_index)
+    z_loss, label_smoothing = float(z_loss), float(label_smoothing)
+    _check_loss_options(z_loss, label_smoothing)
+    if z_loss == 0.0 and label_smoothing == 0.0:
+        loss = _FusedCrossEntropy.apply(hidden, weight, labels, ignore_index, 0.0, 0.0)
+        if return_parts:
+            return loss, loss.detach(), torch.zeros_like(loss)
+        return loss
+    loss, ce, zl = _FusedCrossEntropy.apply(hidden, weight, labels, ignore_index,
+                                            z_loss, label_smoothing)
+    return (loss, ce, zl) if return_parts else loss
 
 
 # ---------------------------------------------------------------------------

@@ -122,6 +122,10 @@ def parse_args(args=None):
     parser.add_argument("--weight_decay", type=float, default=0.0)
     parser.add_argument("--warmup_steps", type=int, default=1_000)
     parser.add_argument("--clip_grad_norm", type=float, default=1.0)
+    # training-loss options (training mode only; eval stays plain cross-entropy)
+    parser.add_argument("--z_loss", type=float, default=0.0,
+                        help="coefficient of the auxiliary z-loss term z * log^2(Z)")
+    parser.add_argument("--label_smoothing", type=float, default=0.0)
 
     parser.add_argument("--eval_every", type=int, default=1_000)
     parser.add_argument("--num_training_steps", type=int, default=10_000)
@@ -471,6 +475,14 @@ def main(args):
                 torch.load(state_path, map_location="cpu", weights_only=True), strict=True
             )
 
+    # runtime loss options sit on the base model, so they stay in force under
+    # the ReLoRA and distributed wrappers
+    loss_options_on = args.z_loss > 0 or args.label_smoothing > 0
+    if loss_options_on:
+        model.set_loss_options(z_loss=args.z_loss, label_smoothing=args.label_smoothing)
+        logger.info(f"Training loss options: z_loss={args.z_loss}, "
+                    f"label_smoothing={args.label_smoothing} (eval reports plain cross-entropy)")
+
     # intra-document masking: doc_start is derived from every batch's
     # input_ids (training and evaluation alike); loss masking is unchanged
     doc_separator_id = None
@@ -704,6 +716,8 @@ def main(args):
     update_time = time.time()
     local_step = 0
     loss_info = torch.tensor([0.0, 0.0, 0.0], device=device)
+    # [ce_loss, z_loss] sums over the accumulation window (loss options only)
+    loss_parts = torch.zeros(2, device=device) if loss_options_on else None
     n_skipped_batches = 0
 
     prof = maybe_make_profiler(args)
@@ -737,8 +751,12 @@ def main(args):
 
         if doc_separator_id is not None:
             batch["doc_start"] = ops.doc_starts_from_eos(batch["input_ids"], doc_separator_id)
-        loss = model(**batch, labels=batch["input_ids"]).loss
+        out = model(**batch, labels=batch["input_ids"])
+        loss = out.loss
 
+        if loss_parts is not None:
+            loss_parts[0] += out.ce_loss
+            loss_parts[1] += out.z_loss
         loss_info[0] += loss.detach()
         loss_info[1] += 1
         loss_info[2] += torch.isnan(loss).float()
@@ -763,6 +781,11 @@ def main(args):
         if dist.is_initialized():
             dist.all_reduce(loss_info, op=dist.ReduceOp.SUM)  # C3: NaN consensus
         _loss = loss_info[0] / loss_info[1]
+        if loss_parts is not None:
+            if dist.is_initialized():
+                dist.all_reduce(loss_parts, op=dist.ReduceOp.SUM)
+            _loss_parts = loss_parts / loss_info[1]
+            loss_parts = torch.zeros_like(loss_parts)
 
         if loss_info[2] == 0:
             optimizer.step()
@@ -842,8 +865,11 @@ def main(args):
         batches_in_update = args.gradient_accumulation * world_size
 
         if global_rank == 0:
+            loss_parts_log = ({"ce_loss": float(_loss_parts[0]), "z_loss": float(_loss_parts[1])}
+                              if loss_options_on else {})
             wandb.log({
                 "loss": float(_loss),
+                **loss_parts_log,
                 "lr": lr,
                 "update_step": update_step,
                 "tokens_seen": tokens_seen,
