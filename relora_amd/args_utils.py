@@ -124,6 +124,20 @@ def check_args_torchrun_main(args, n_cli_args=None):
     if not 0 <= args.label_smoothing < 1:
         raise ValueError(f"--label_smoothing must be in [0, 1), got {args.label_smoothing}")
 
+    args.adam_state_dtype = getattr(args, "adam_state_dtype", None) or "param"
+    args.adam_rounding = getattr(args, "adam_rounding", None) or "nearest"
+    if args.adam_state_dtype not in ("param", "float32"):
+        raise ValueError(
+            f"--adam_state_dtype must be 'param' or 'float32', got {args.adam_state_dtype!r}")
+    if args.adam_rounding not in ("nearest", "stochastic"):
+        raise ValueError(
+            f"--adam_rounding must be 'nearest' or 'stochastic', got {args.adam_rounding!r}")
+    if getattr(args, "adam_rounding_seed", None) is None:
+        args.adam_rounding_seed = int(args.seed)
+    args.adam_rounding_seed = int(args.adam_rounding_seed)
+    if not -(1 << 63) <= args.adam_rounding_seed < (1 << 63):
+        raise ValueError("--adam_rounding_seed must fit in 64 bits")
+
     if getattr(args, "intra_doc_masking", False) and _is_pythia_run(args):
         raise ValueError(
             "--intra_doc_masking is implemented for the LLaMA models only; "

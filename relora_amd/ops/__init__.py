@@ -19,3 +19,4 @@ from relora_amd.ops.functional import (  # noqa: F401
     swiglu_torch,
 )
 from relora_amd.ops import hip  # noqa: F401
+from relora_amd.ops.optim import stochastic_round_bf16  # noqa: F401

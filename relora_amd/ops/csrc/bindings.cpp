@@ -40,6 +40,13 @@ void fused_adamw(std::vector<torch::Tensor> params, std::vector<torch::Tensor> g
                  double lr, double beta1, double beta2, double eps, double wd, long step);
 torch::Tensor multi_tensor_l2norm(std::vector<torch::Tensor> grads);
 void multi_tensor_scale_(std::vector<torch::Tensor> grads, double scale);
+// adamw_ex.hip
+void fused_adamw_ex(std::vector<torch::Tensor> params, std::vector<torch::Tensor> grads,
+                    std::vector<torch::Tensor> exp_avgs, std::vector<torch::Tensor> exp_avg_sqs,
+                    double lr, double beta1, double beta2, double eps, double wd, long step,
+                    bool stochastic, int64_t seed, std::vector<int64_t> ordinals);
+torch::Tensor stochastic_round_bf16_op(torch::Tensor x, int64_t seed, long step, long ordinal,
+                                       long lane);
 // lora_gemm.hip
 std::vector<torch::Tensor> dropout_mask_fwd(torch::Tensor x, double p, int64_t seed);
 torch::Tensor dropout_mask_bwd(torch::Tensor dy, torch::Tensor mask, double p);
@@ -106,6 +113,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ce_grad_ex_", &ce_grad_ex_,
         "CE in-place grad with z-loss and label smoothing (gfx950)");
   m.def("fused_adamw", &fused_adamw, "multi-tensor AdamW step (gfx950)");
+  m.def("fused_adamw_ex", &fused_adamw_ex,
+        "multi-tensor AdamW step, bf16 params with fp32 moments and/or stochastic rounding "
+        "(gfx950)",
+        py::arg("params"), py::arg("grads"), py::arg("exp_avgs"), py::arg("exp_avg_sqs"),
+        py::arg("lr"), py::arg("beta1"), py::arg("beta2"), py::arg("eps"), py::arg("wd"),
+        py::arg("step"), py::arg("stochastic"), py::arg("seed"), py::arg("ordinals"));
+  m.def("stochastic_round_bf16", &stochastic_round_bf16_op,
+        "fp32 -> bf16 stochastic rounding with Philox4x32-10 bits (gfx950)",
+        py::arg("x"), py::arg("seed"), py::arg("step"), py::arg("ordinal"), py::arg("lane"));
   m.def("multi_tensor_l2norm", &multi_tensor_l2norm, "multi-tensor L2 norm (gfx950)");
   m.def("multi_tensor_scale_", &multi_tensor_scale_, "multi-tensor scale (gfx950)");
   m.def("dropout_mask_fwd", &dropout_mask_fwd, "fused dropout + packed mask (gfx950)");

@@ -49,6 +49,10 @@ class ZeroRedundancyAdamW:
         self.optim = AdamW(self.shard_params if self.shard_params else
                            [torch.nn.Parameter(torch.zeros(1))], **adamw_kwargs)
         self._have_params = bool(self.shard_params)
+        if self._have_params:
+            # stochastic-rounding counters use the position among ALL params,
+            # so the drawn bits do not depend on the world size
+            self.optim.set_ordinals([self._param_index[id(p)] for p in self.shard_params])
 
         # flat broadcast buffers, one per owner rank
         self._rank_params = [
@@ -161,6 +165,12 @@ class ZeroRedundancyAdamW:
             p = self.all_params[idx]
             if self.owner[idx] != self.rank:
                 continue
+            # moments land in the shard optimizer's moment dtype (fp32 under
+            # state_dtype=float32, else the parameter's), as AdamW.load_state_dict
+            moment_dtype = self.optim._moment_dtype(p)
             self.optim.state[p] = {
-                k: (v.to(p.device) if torch.is_tensor(v) else v) for k, v in st.items()
+                k: ((v.to(device=p.device, dtype=moment_dtype)
+                     if k in ("exp_avg", "exp_avg_sq") else v.to(p.device))
+                    if torch.is_tensor(v) else v)
+                for k, v in st.items()
             }

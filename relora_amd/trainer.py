@@ -120,6 +120,15 @@ def parse_args(args=None):
     parser.add_argument("--adam_beta1", type=float, default=0.9)
     parser.add_argument("--adam_beta2", type=float, default=0.999)
     parser.add_argument("--weight_decay", type=float, default=0.0)
+    # optimizer number formats for bf16 training (no effect with --dtype float32)
+    parser.add_argument("--adam_state_dtype", type=str, default="param",
+                        help="dtype of the Adam moments: 'param' (the parameter's dtype) or "
+                             "'float32'")
+    parser.add_argument("--adam_rounding", type=str, default="nearest",
+                        help="rounding of bf16 parameter/moment writes: 'nearest' or "
+                             "'stochastic'")
+    parser.add_argument("--adam_rounding_seed", type=int, default=None,
+                        help="seed of the stochastic-rounding bits. Default: --seed")
     parser.add_argument("--warmup_steps", type=int, default=1_000)
     parser.add_argument("--clip_grad_norm", type=float, default=1.0)
     # training-loss options (training mode only; eval stays plain cross-entropy)
@@ -612,7 +621,17 @@ def main(args):
         "lr": args.lr,
         "weight_decay": args.weight_decay,
         "betas": (args.adam_beta1, args.adam_beta2),
+        "state_dtype": torch.float32 if args.adam_state_dtype == "float32" else None,
+        "rounding": args.adam_rounding,
+        "rounding_seed": args.adam_rounding_seed,
     }
+    adam_options_on = args.adam_state_dtype != "param" or args.adam_rounding != "nearest"
+    if adam_options_on and args.dtype in ["fp32", "float32"]:
+        logger.info("--adam_state_dtype / --adam_rounding have no effect with --dtype float32: "
+                    "the moments are already fp32 and nothing is rounded to bf16")
+    elif adam_options_on:
+        logger.info(f"AdamW number formats: state_dtype={args.adam_state_dtype}, "
+                    f"rounding={args.adam_rounding}, rounding_seed={args.adam_rounding_seed}")
     if args.optimizer.lower() == "adam":
         optimizer = AdamW(trainable_params, **optimizer_kwargs)
     elif args.optimizer.lower() == "adam_zero":

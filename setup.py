@@ -35,6 +35,7 @@ ext = CUDAExtension(
         os.path.join(CSRC, "swiglu.hip"),
         os.path.join(CSRC, "ce.hip"),
         os.path.join(CSRC, "adamw.hip"),
+        os.path.join(CSRC, "adamw_ex.hip"),
         os.path.join(CSRC, "attention.hip"),
         os.path.join(CSRC, "lora_gemm.hip"),
         os.path.join(CSRC, "lora_group.cpp"),
