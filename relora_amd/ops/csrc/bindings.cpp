@@ -63,7 +63,7 @@ std::vector<torch::Tensor> lora_group_bwd(
     std::vector<torch::Tensor> dys, torch::Tensor x, std::vector<torch::Tensor> masks,
     std::vector<torch::Tensor> ts, std::vector<torch::Tensor> Ws,
     std::vector<torch::Tensor> As, std::vector<torch::Tensor> bss,
-    std::vector<double> scales, double p);
+    std::vector<double> scales, double p, bool group_bwd);
 
 // fused_gemm.hip
 torch::Tensor fused_lora_gemm(torch::Tensor x, torch::Tensor w, torch::Tensor t,
@@ -83,6 +83,12 @@ void lora_add_nn_(torch::Tensor out, torch::Tensor P, torch::Tensor Q,
 torch::Tensor skinny_grad(torch::Tensor P, torch::Tensor X, torch::Tensor xmask,
                           double inv_keep, double scale,
                           bool transpose_out, torch::ScalarType dtype);
+void lora_add_nn_group_(torch::Tensor out, std::vector<torch::Tensor> Ps,
+                        std::vector<torch::Tensor> Qs, std::vector<torch::Tensor> masks,
+                        double inv_keep);
+std::vector<torch::Tensor> skinny_grad_group(std::vector<torch::Tensor> Ps, torch::Tensor X,
+                                             std::vector<torch::Tensor> masks,
+                                             double inv_keep, torch::ScalarType dtype);
 // quantize.hip
 std::vector<torch::Tensor> quantize_nf4(torch::Tensor x);
 torch::Tensor dequantize_nf4(torch::Tensor q, torch::Tensor absmax, long n, torch::ScalarType dtype);
@@ -132,7 +138,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lora_group_fwd", &lora_group_fwd,
         "group LoRA linear forward for siblings sharing one input (gfx950)");
   m.def("lora_group_bwd", &lora_group_bwd,
-        "group LoRA linear backward into one shared dx (gfx950)");
+        "group LoRA linear backward into one shared dx (gfx950)",
+        py::arg("dys"), py::arg("x"), py::arg("masks"), py::arg("ts"), py::arg("Ws"),
+        py::arg("As"), py::arg("bss"), py::arg("scales"), py::arg("p"),
+        py::arg("group_bwd") = true);
   m.def("fused_lora_gemm", &fused_lora_gemm,
         "y = x@W^T (+bias) + s*t@Bw^T fused MFMA GEMM, 256^2 glds tile (gfx950)");
   m.def("fused_lora_gemm3", &fused_lora_gemm3,
@@ -145,6 +154,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "y = x@dequant(W)^T + s*t@Bw^T with NF4 dequant fused into LDS staging (gfx950)");
   m.def("lora_add_nn_", &lora_add_nn_, "out += maskscale*(P @ Q) rank-r MFMA accumulate (gfx950)");
   m.def("skinny_grad", &skinny_grad, "P^T @ X chunked fp32 reduction (gfx950)");
+  m.def("lora_add_nn_group_", &lora_add_nn_group_,
+        "out += sum_g maskscale_g*(P_g @ Q_g), one pass over out for 1..3 siblings (gfx950)");
+  m.def("skinny_grad_group", &skinny_grad_group,
+        "P_g^T @ mask_g(X) for 1..3 siblings, X read once (gfx950)");
   m.def("quantize_nf4", &quantize_nf4, "NF4 blockwise quantize (gfx950)");
   m.def("dequantize_nf4", &dequantize_nf4, "NF4 blockwise dequantize (gfx950)");
   m.def("quantize_int8", &quantize_int8, "int8 blockwise quantize (gfx950)");

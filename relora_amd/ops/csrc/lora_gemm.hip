@@ -414,6 +414,250 @@ void lora_add_nn_(torch::Tensor out, torch::Tensor P, torch::Tensor Q,
 }
 
 // ---------------------------------------------------------------------------
+// Group form of the dx epilogue: out[M,N] += sum_g maskscale_g * (P_g @ Q_g)
+// for G <= 3 siblings that accumulate into the same out (q/k/v, gate/up), as
+// ONE read-modify-write of out instead of G.
+//
+// Same 128x128 tile, 4 waves and staging as lora_skinny_kernel<true, MASK>.
+// Per sibling: stage P_g and the rotated Q_g^T tile, run the MFMAs, dump the
+// C layout through LDS (fp32 here, so a contribution is not rounded before it
+// is summed) and add the mask-selected, inv_keep-scaled values into a
+// per-thread fp32 running sum laid out like the final bf16x8 pieces (8 pieces
+// of 8 per thread).  The out pieces do not depend on any of that, so their
+// loads are issued first, in flight under the first sibling's staging and
+// MFMA work, and start the running sum; the old out and the G contributions
+// are summed in fp32 and rounded once.
+// ---------------------------------------------------------------------------
+
+struct LoraAddGroupArgs {
+  const __hip_bfloat16* P[3];
+  const __hip_bfloat16* Q[3];
+  const uint8_t* mask[3];
+};
+
+template <bool MASK>
+__global__ __launch_bounds__(256, 2) void lora_skinny_group_kernel(
+    LoraAddGroupArgs a, int G, __hip_bfloat16* __restrict__ out, float inv_keep,
+    long M, int N, int r) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int ldt = r + LPAD;
+  // whole 64-element rotation blocks per transposed row, as lora_skinny_kernel
+  const int ldq_t = ((r + 63) & ~63) + LPAD;
+  __bf16* p_im = (__bf16*)smem;         // [128][ldt]
+  __bf16* q_im = p_im + 128 * ldt;      // [128][ldq_t]
+  constexpr int OLDF = 128 + 4;         // fp32 out-tile stride (16 B pad)
+  float* o_im = (float*)smem;           // [128][OLDF], aliases p_im/q_im
+
+  const long m0 = (long)blockIdx.y * 128;
+  const int n0 = blockIdx.x * 128;
+
+  // this thread's 8 out pieces: rows prow + 16 i, columns n .. n + 7, at
+  // 32-bit offsets from the tile's first element (flat index base_flat; mask
+  // bits are FLAT-packed over [M*N], so bit base_lo of byte base_flat >> 3)
+  const int prow = threadIdx.x >> 4;
+  const int c8 = (threadIdx.x & 15) * 8;
+  const int n = n0 + c8;
+  const long base_flat = m0 * (long)N + n0;
+  const unsigned base_lo = (unsigned)(base_flat & 7);
+  __hip_bfloat16* obase = out + base_flat;
+  const int mrem = (int)min(M - m0, 128L);  // valid rows of the tile
+  auto piece_off = [&](int i) { return base_lo + (unsigned)(prow + i * 16) * N + c8; };
+  auto piece_ok = [&](int i) { return prow + i * 16 < mrem && n < N; };
+  auto piece_vec = [&](int i) {
+    return prow + i * 16 < mrem && n + 8 <= N && (piece_off(i) & 7) == 0;
+  };
+  // fp32 running sum, started from the old out where the piece is one
+  // aligned bf16x8 (pieces of the unaligned path start at 0 and add the old
+  // values in the final scalar read-modify-write)
+  float sum[8][8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    if (piece_vec(i)) {
+      const Vec8<__hip_bfloat16> ov = load8(obase + (piece_off(i) - base_lo));
+#pragma unroll
+      for (int j = 0; j < 8; ++j) sum[i][j] = to_f32(ov.v[j]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) sum[i][j] = 0.f;
+    }
+  }
+
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int wr = (wave >> 1) * 64;  // wave row offset in tile
+  const int wc = (wave & 1) * 64;   // wave col offset
+  const int fr = lane & 15;         // fragment row/col
+  const int kg = (lane >> 4) * 8;   // k-group offset
+  const int crow = (lane >> 4) * 4; // C-frag rows crow..crow+3, col = fr
+
+  for (int g = 0; g < G; ++g) {
+    const __hip_bfloat16* P = g == 0 ? a.P[0] : (g == 1 ? a.P[1] : a.P[2]);
+    const __hip_bfloat16* Q = g == 0 ? a.Q[0] : (g == 1 ? a.Q[1] : a.Q[2]);
+    const uint8_t* mbase =
+        (g == 0 ? a.mask[0] : (g == 1 ? a.mask[1] : a.mask[2])) + (base_flat >> 3);
+    if (g) __syncthreads();  // the previous sibling's o_im reads are done
+
+    // stage P rows [128][r]
+    for (int t = threadIdx.x; t < 128 * (r / 8); t += blockDim.x) {
+      const int row = t / (r / 8);
+      const int c = (t % (r / 8)) * 8;
+      bf16x8 v;
+      if (m0 + row < M) {
+        v = *reinterpret_cast<const bf16x8*>(P + (m0 + row) * (long)r + c);
+      } else {
+        v = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+      }
+      *reinterpret_cast<bf16x8*>(p_im + rm_idx(row, c, ldt)) = v;
+    }
+    // Q is [r][N]: q_im[n][k] = Q[k][n0+n], rotated (see lora_skinny_kernel)
+    for (int t = threadIdx.x; t < r * 16; t += blockDim.x) {
+      const int k = t / 16;
+      const int nb = (t % 16) * 8;
+      bf16x8 v;
+      if (n0 + nb + 8 <= N) {
+        v = *reinterpret_cast<const bf16x8*>(Q + (long)k * N + n0 + nb);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          v[j] = (n0 + nb + j < N) ? (__bf16)Q[(long)k * N + n0 + nb + j] : (__bf16)0.f;
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        q_im[(nb + j) * ldq_t + trq_off(nb + j, k, r)] = v[j];
+    }
+    // mask bytes of the aligned pieces; loaded before the MFMA loop, used
+    // after it
+    uint32_t mb[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      mb[i] = 0xFF;
+      if (MASK && piece_vec(i)) mb[i] = mbase[piece_off(i) >> 3];
+    }
+    __syncthreads();
+
+    f32x4 acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int kk = 0; kk < r; kk += 32) {
+#pragma unroll
+      for (int mi = 0; mi < 4; ++mi) {
+        const bf16x8 av =
+            *reinterpret_cast<const bf16x8*>(p_im + rm_idx(wr + mi * 16 + fr, kk + kg, ldt));
+#pragma unroll
+        for (int ni = 0; ni < 4; ++ni) {
+          const int qrow = wc + ni * 16 + fr;
+          const bf16x8 bv = *reinterpret_cast<const bf16x8*>(
+              q_im + qrow * ldq_t + trq_off(qrow, kk + kg, r));
+          acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, bv, acc[mi][ni], 0, 0, 0);
+        }
+      }
+    }
+
+    __syncthreads();  // done with p_im/q_im; reuse the LDS as the out tile
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+      for (int ni = 0; ni < 4; ++ni)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          o_im[(wr + mi * 16 + crow + j) * OLDF + wc + ni * 16 + fr] = acc[mi][ni][j];
+    __syncthreads();
+
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const float* src = o_im + (prow + i * 16) * OLDF + c8;
+      const f32x4 s0 = *reinterpret_cast<const f32x4*>(src);
+      const f32x4 s1 = *reinterpret_cast<const f32x4*>(src + 4);
+      if (MASK && !piece_vec(i) && piece_ok(i)) {
+        // unaligned rows (odd N) or the row tail: gather the 8 bits
+        const unsigned off = piece_off(i);
+        mb[i] = 0;
+        for (int j = 0; j < 8 && n + j < N; ++j)
+          mb[i] |= ((uint32_t)(mbase[(off + j) >> 3] >> ((off + j) & 7)) & 1u) << j;
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float v = j < 4 ? s0[j] : s1[j - 4];
+        if (MASK) sum[i][j] += (mb[i] >> j) & 1 ? v * inv_keep : 0.f;
+        else sum[i][j] += v;
+      }
+    }
+  }
+
+  // one read-modify-write of out
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    if (!piece_ok(i)) continue;
+    __hip_bfloat16* o = obase + (piece_off(i) - base_lo);
+    if (piece_vec(i)) {
+      Vec8<__hip_bfloat16> ov;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) ov.v[j] = from_f32<__hip_bfloat16>(sum[i][j]);
+      store8(o, ov);
+    } else {  // unaligned rows (odd N) or the row tail
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        if (n + j < N) o[j] = from_f32<__hip_bfloat16>(to_f32(o[j]) + sum[i][j]);
+    }
+  }
+}
+
+// out[M,K] += sum_g maskscale * (Ps[g][M,r] @ Qs[g][r,K]), G = 1..3 siblings
+// sharing one r; masks empty -> no dropout.  One rounding of out to bf16.
+void lora_add_nn_group_(torch::Tensor out, std::vector<torch::Tensor> Ps,
+                        std::vector<torch::Tensor> Qs, std::vector<torch::Tensor> masks,
+                        double inv_keep) {
+  const int G = (int)Ps.size();
+  TORCH_CHECK(G >= 1 && G <= 3 && (int)Qs.size() == G,
+              "lora_add_nn_group_: 1..3 siblings, one Q per P");
+  TORCH_CHECK(masks.empty() || (int)masks.size() == G,
+              "lora_add_nn_group_: no masks or one per sibling");
+  TORCH_CHECK(out.is_cuda() && out.is_contiguous() && out.dim() == 2,
+              "lora_add_nn_group_: out must be a contiguous [M,K] tensor");
+  TORCH_CHECK(out.scalar_type() == torch::kBFloat16, "lora_add: bf16 only");
+  const long M = out.size(0);
+  const int N = out.size(1);
+  TORCH_CHECK(Ps[0].dim() == 2, "lora_add_nn_group_: P_g must be [M,r]");
+  const int r = Ps[0].size(1);
+  TORCH_CHECK(r % 32 == 0 && r <= 256, "lora_add: r must be a multiple of 32, <=256");
+  const bool has_mask = !masks.empty();
+  LoraAddGroupArgs a = {};
+  for (int g = 0; g < G; ++g) {
+    const auto& P = Ps[g];
+    const auto& Q = Qs[g];
+    TORCH_CHECK(P.is_cuda() && Q.is_cuda() && P.is_contiguous() && Q.is_contiguous() &&
+                P.scalar_type() == torch::kBFloat16 && Q.scalar_type() == torch::kBFloat16,
+                "lora_add_nn_group_: P_g, Q_g must be contiguous bf16");
+    TORCH_CHECK(P.dim() == 2 && Q.dim() == 2 && P.size(1) == r && Q.size(0) == r,
+                "lora_add_nn_group_: every sibling must have the same r");
+    TORCH_CHECK(P.size(0) == M && Q.size(1) == N, "lora_add_nn_group_: shape mismatch");
+    a.P[g] = (const __hip_bfloat16*)P.data_ptr();
+    a.Q[g] = (const __hip_bfloat16*)Q.data_ptr();
+    if (has_mask) {
+      TORCH_CHECK(masks[g].is_cuda() && masks[g].is_contiguous() &&
+                  masks[g].scalar_type() == torch::kUInt8 &&
+                  masks[g].numel() == (M * (long)N + 7) / 8, "mask size mismatch");
+      a.mask[g] = masks[g].data_ptr<uint8_t>();
+    }
+  }
+  if (M == 0 || N == 0) return;
+  auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
+  const size_t lds = std::max<size_t>(
+      (128u * (r + LPAD) + 128u * (((r + 63) & ~63) + LPAD)) * sizeof(__bf16),
+      128u * (128 + 4) * sizeof(float));
+  dim3 grid((N + 127) / 128, (M + 127) / 128), block(256);
+  if (has_mask)
+    hipLaunchKernelGGL((lora_skinny_group_kernel<true>), grid, block, lds, stream, a, G,
+                       (__hip_bfloat16*)out.data_ptr(), (float)inv_keep, M, N, r);
+  else
+    hipLaunchKernelGGL((lora_skinny_group_kernel<false>), grid, block, lds, stream, a, G,
+                       (__hip_bfloat16*)out.data_ptr(), 1.f, M, N, r);
+  HIP_CHECK_LAST();
+}
+
+// ---------------------------------------------------------------------------
 // LoRA weight gradients: out[r, C] = P[M, r]^T @ X[M, C], fp32 partials per
 // M-chunk (deterministic tree sum in the caller).  hipBLASLt runs these
 // skinny-output reductions as 32-workgroup launches (12% of the chip);
@@ -633,6 +877,285 @@ torch::Tensor skinny_grad(torch::Tensor P, torch::Tensor X, torch::Tensor xmask,
   }
   HIP_CHECK_LAST();
   return out;
+}
+
+// ---------------------------------------------------------------------------
+// Group form of the dA gradient: out_g[r, C] = P_g[M, r]^T @ dropout_g(X)[M, C]
+// for G <= 3 siblings that share X (q/k/v, gate/up).  Each 64-row x 128-column
+// X tile is loaded from global memory ONCE and masked G ways while it is
+// staged into G rotated X^T tiles; the P_g^T tiles are staged as in
+// skinny_grad_kernel.  Same chunks, m-tiles, k-steps and MFMA as
+// skinny_grad_kernel, so every output element sees the same sequence of fp32
+// accumulations: the results equal G skinny_grad calls bit for bit.
+//
+// Block = 512 threads = 8 waves; wave w owns output rows w*16 .. w*16+15 of
+// every sibling (8 column fragments each: 32 accumulator registers per
+// sibling).  LDS holds ONE buffer of G P^T and G X^T tiles (G * 32 KiB; 96 KiB
+// at G = 3, which a double buffer would push past the 160 KiB of a CU).  The
+// overlap a second buffer gave comes from registers instead: the global loads
+// of m-tile t+1 are issued before the MFMA work of tile t and written to LDS
+// after it (two barriers per tile).
+//
+// grid: (C/128, MCHUNKS, r/128).  part is [chunks][G][r][C] fp32.
+// ---------------------------------------------------------------------------
+
+struct SkinnyGroupArgs {
+  const __hip_bfloat16* P[3];
+  const uint8_t* mask[3];
+};
+
+template <int G, bool MASK>
+__global__ __launch_bounds__(512) void skinny_grad_group_kernel(
+    SkinnyGroupArgs a, const __hip_bfloat16* __restrict__ X, float inv_keep,
+    float* __restrict__ part, long M, int C, int r, int rows_per_chunk) {
+  constexpr int NX = MASK ? G : 1;      // without masks every sibling reads one X^T
+  const int r0 = blockIdx.z * 128;      // r-tile (rank 256 spans two)
+  const int rtile = min(r - r0, 128);
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  __bf16* pt = (__bf16*)smem;           // [G][128][64] rotated: P_g^T tiles
+  __bf16* xt = pt + G * 128 * 64;       // [NX][128][64] rotated: masked X^T tiles
+
+  const int c0 = blockIdx.x * 128;
+  const long m_begin = (long)blockIdx.y * rows_per_chunk;
+  const long m_end = min(M, m_begin + rows_per_chunk);
+
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int col = lane & 15;
+  const int kgrp = lane >> 4;
+
+  f32x4 acc[G][8];
+#pragma unroll
+  for (int g = 0; g < G; ++g)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[g][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  // staging pieces of one m-tile, two per thread and tensor:
+  //   X: piece t = tid + 512 i -> row t / 16, columns (t % 16) * 8 .. + 7
+  //   P_g: piece t -> row t / (rtile / 8), ranks (t % (rtile / 8)) * 8 .. + 7
+  const int p8 = rtile / 8;
+  bf16x8 xreg[2], preg[G][2];
+  uint8_t mreg[NX][2];
+
+  auto gload = [&](long m0) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int t = threadIdx.x + i * 512;
+      const int mm = t / 16;
+      const int c8 = (t % 16) * 8;
+      // 32-bit element offset (the host checks M * C < 2^31); C % 8 == 0, so
+      // the 8 mask bits are one byte
+      const unsigned xoff = (unsigned)(m0 + mm) * C + c0 + c8;
+      if (m0 + mm < m_end && c0 + c8 < C) {
+        xreg[i] = *reinterpret_cast<const bf16x8*>(X + xoff);
+        if (MASK) {
+#pragma unroll
+          for (int g = 0; g < NX; ++g) mreg[g][i] = a.mask[g][xoff >> 3];
+        }
+      } else {
+        xreg[i] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+        for (int g = 0; g < NX; ++g) mreg[g][i] = 0;
+      }
+    }
+#pragma unroll
+    for (int g = 0; g < G; ++g)
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const int t = threadIdx.x + i * 512;
+        const int mm = t / p8;
+        const int j8 = (t % p8) * 8;
+        if (t < 64 * p8 && m0 + mm < m_end) {
+          preg[g][i] = *reinterpret_cast<const bf16x8*>(
+              a.P[g] + ((unsigned)(m0 + mm) * r + r0 + j8));
+        } else {
+          preg[g][i] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+        }
+      }
+  };
+
+  auto lstore = [&]() {
+    // the LDS addresses below are loop invariants that would be kept in ~32
+    // registers across the MFMA work; hiding the thread index from the
+    // optimiser has them recomputed per tile (a few VALU ops each) instead
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+#pragma unroll
+    for (int g = 0; g < G; ++g)
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const int t = tid + i * 512;
+        const int mm = t / p8;
+        const int j8 = (t % p8) * 8;
+        if (t < 64 * p8) {
+          __bf16* ptg = pt + g * 128 * 64;
+#pragma unroll
+          for (int j = 0; j < 8; ++j) ptg[tr64(j8 + j, mm)] = preg[g][i][j];
+        }
+      }
+#pragma unroll
+    for (int g = 0; g < NX; ++g)
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const int t = tid + i * 512;
+        const int mm = t / 16;
+        const int c8 = (t % 16) * 8;
+        __bf16* xtg = xt + g * 128 * 64;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          __bf16 v = xreg[i][j];
+          // kept values: the rounding of skinny_grad_kernel, bf16(x * inv_keep)
+          if (MASK) v = (mreg[g][i] >> j) & 1 ? (__bf16)((float)v * inv_keep) : (__bf16)0.f;
+          xtg[tr64(c8 + j, mm)] = v;
+        }
+      }
+  };
+
+  const int jrow = wave * 16 + col;
+  gload(m_begin);
+  for (long m0 = m_begin; m0 < m_end; m0 += 64) {
+    lstore();
+    __syncthreads();
+    if (m0 + 64 < m_end) gload(m0 + 64);  // in flight under the MFMA work
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        const __bf16* ptg = pt + g * 128 * 64;
+        const __bf16* xtg = xt + (MASK ? g : 0) * 128 * 64;
+        const bf16x8 av = (jrow < rtile)
+            ? *reinterpret_cast<const bf16x8*>(ptg + tr64(jrow, ks * 32 + kgrp * 8))
+            : bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const bf16x8 bv = *reinterpret_cast<const bf16x8*>(
+              xtg + tr64(j * 16 + col, ks * 32 + kgrp * 8));
+          acc[g][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, bv, acc[g][j], 0, 0, 0);
+        }
+      }
+    }
+    __syncthreads();  // the tiles are free for the next lstore
+  }
+
+  // epilogue: fp32 partial planes [chunk][g]
+  const int rbase = wave * 16 + (kgrp << 2);
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    float* plane = part + ((long)blockIdx.y * G + g) * r * C;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int c = c0 + j * 16 + col;
+      if (c >= C) continue;
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        const int rr = rbase + reg;
+        if (rr < rtile) plane[(long)(r0 + rr) * C + c] = acc[g][j][reg];
+      }
+    }
+  }
+}
+
+// out[g][e] = sum_chunks part[chunk][g][e], e over one [r, C] plane; the same
+// sequential fp32 sum per element as skinny_combine_kernel
+template <typename T>
+__global__ void skinny_combine_group_kernel(const float* __restrict__ part,
+                                            T* __restrict__ out, long plane, int G,
+                                            int nchunks) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= plane * G) return;
+  float acc = 0.f;
+  for (int c = 0; c < nchunks; ++c) acc += part[(long)c * G * plane + i];
+  out[i] = from_f32<T>(acc);
+}
+
+template <int G>
+static void launch_skinny_group(bool has_mask, dim3 grid, size_t lds, hipStream_t stream,
+                                const SkinnyGroupArgs& a, const __hip_bfloat16* X,
+                                float inv_keep, float* part, long M, int C, int r, int rows) {
+  if (has_mask)
+    hipLaunchKernelGGL((skinny_grad_group_kernel<G, true>), grid, dim3(512), lds, stream, a,
+                       X, inv_keep, part, M, C, r, rows);
+  else
+    hipLaunchKernelGGL((skinny_grad_group_kernel<G, false>), grid, dim3(512), lds, stream, a,
+                       X, 1.f, part, M, C, r, rows);
+}
+
+// {P_g[M,r]^T @ dropout_mask_g(X)[M,C]} in `dtype`, G = 1..3 siblings sharing X
+// and r; the meaning of skinny_grad(P_g, X, mask_g, inv_keep, 1.0, false, dtype)
+// per sibling.  masks empty -> X used as-is.  The G results are the planes of
+// one [G, r, C] tensor.
+std::vector<torch::Tensor> skinny_grad_group(std::vector<torch::Tensor> Ps, torch::Tensor X,
+                                             std::vector<torch::Tensor> masks,
+                                             double inv_keep, torch::ScalarType dtype) {
+  const int G = (int)Ps.size();
+  TORCH_CHECK(G >= 1 && G <= 3, "skinny_grad_group: 1..3 siblings");
+  TORCH_CHECK(masks.empty() || (int)masks.size() == G,
+              "skinny_grad_group: no masks or one per sibling");
+  TORCH_CHECK(X.is_cuda() && X.is_contiguous() && X.dim() == 2 &&
+              X.scalar_type() == torch::kBFloat16,
+              "skinny_grad_group: X must be a contiguous bf16 [M,C] tensor");
+  TORCH_CHECK(dtype == torch::kBFloat16 || dtype == torch::kFloat32,
+              "skinny_grad: bf16 or fp32 output");
+  const long M = X.size(0);
+  const int C = X.size(1);
+  TORCH_CHECK(Ps[0].dim() == 2, "skinny_grad_group: P_g must be [M,r]");
+  const int r = Ps[0].size(1);
+  TORCH_CHECK(M >= 1 && C >= 8 && C % 8 == 0,
+              "skinny_grad_group: C must be a multiple of 8");
+  TORCH_CHECK(M * (long)std::max(C, r) < (1L << 31),
+              "skinny_grad_group: M * C must be below 2^31 (32-bit offsets in the kernel)");
+  TORCH_CHECK(r % 8 == 0 && r >= 8 && r <= 256, "skinny_grad_group: r % 8 == 0, r <= 256");
+  const bool has_mask = !masks.empty();
+  SkinnyGroupArgs a = {};
+  for (int g = 0; g < G; ++g) {
+    const auto& P = Ps[g];
+    TORCH_CHECK(P.is_cuda() && P.is_contiguous() && P.scalar_type() == torch::kBFloat16 &&
+                P.dim() == 2 && P.size(0) == M, "skinny_grad_group: P_g must be contiguous bf16 [M,r]");
+    TORCH_CHECK(P.size(1) == r, "skinny_grad_group: every sibling must have the same r");
+    a.P[g] = (const __hip_bfloat16*)P.data_ptr();
+    if (has_mask) {
+      TORCH_CHECK(masks[g].is_cuda() && masks[g].is_contiguous() &&
+                  masks[g].scalar_type() == torch::kUInt8 &&
+                  masks[g].numel() == (M * (long)C + 7) / 8, "skinny_grad mask size");
+      a.mask[g] = masks[g].data_ptr<uint8_t>();
+    }
+  }
+  // the chunk rule of skinny_grad
+  int chunks = 1;
+  const int ctiles = (C + 127) / 128;
+  while (chunks < 32 && ctiles * chunks < 512 && (M + chunks - 1) / chunks > 256)
+    chunks <<= 1;
+  int rows = (int)((M + chunks - 1) / chunks);
+  rows = (rows + 63) / 64 * 64;  // multiple of the m-tile
+  chunks = (int)((M + rows - 1) / rows);
+  const long plane = (long)r * C;
+  auto part = torch::empty({chunks, G, r, C}, X.options().dtype(torch::kFloat32));
+  auto out = torch::empty({G, r, C}, X.options().dtype(dtype));
+  auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
+  const size_t lds = (size_t)(G + (has_mask ? G : 1)) * 128 * 64 * sizeof(__bf16);
+  dim3 grid(ctiles, chunks, (r + 127) / 128);
+  const __hip_bfloat16* xp = (const __hip_bfloat16*)X.data_ptr();
+  switch (G) {
+    case 1: launch_skinny_group<1>(has_mask, grid, lds, stream, a, xp, (float)inv_keep,
+                                   part.data_ptr<float>(), M, C, r, rows); break;
+    case 2: launch_skinny_group<2>(has_mask, grid, lds, stream, a, xp, (float)inv_keep,
+                                   part.data_ptr<float>(), M, C, r, rows); break;
+    default: launch_skinny_group<3>(has_mask, grid, lds, stream, a, xp, (float)inv_keep,
+                                    part.data_ptr<float>(), M, C, r, rows); break;
+  }
+  HIP_CHECK_LAST();
+  dim3 cgrid((plane * G + 255) / 256), cblock(256);
+  if (dtype == torch::kBFloat16)
+    hipLaunchKernelGGL((skinny_combine_group_kernel<__hip_bfloat16>), cgrid, cblock, 0, stream,
+                       part.data_ptr<float>(), (__hip_bfloat16*)out.data_ptr(), plane, G,
+                       chunks);
+  else
+    hipLaunchKernelGGL((skinny_combine_group_kernel<float>), cgrid, cblock, 0, stream,
+                       part.data_ptr<float>(), out.data_ptr<float>(), plane, G, chunks);
+  HIP_CHECK_LAST();
+  std::vector<torch::Tensor> outs;
+  for (int g = 0; g < G; ++g) outs.push_back(out.select(0, g));
+  return outs;
 }
 
 torch::Tensor dropout_mask_bwd(torch::Tensor dy, torch::Tensor mask, double p) {

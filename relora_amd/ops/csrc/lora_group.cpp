@@ -22,6 +22,12 @@ torch::Tensor fused_lora_gemm(torch::Tensor x, torch::Tensor w, torch::Tensor t,
 torch::Tensor skinny_grad(torch::Tensor P, torch::Tensor X, torch::Tensor xmask,
                           double inv_keep, double scale,
                           bool transpose_out, torch::ScalarType dtype);
+void lora_add_nn_group_(torch::Tensor out, std::vector<torch::Tensor> Ps,
+                        std::vector<torch::Tensor> Qs, std::vector<torch::Tensor> masks,
+                        double inv_keep);
+std::vector<torch::Tensor> skinny_grad_group(std::vector<torch::Tensor> Ps, torch::Tensor X,
+                                             std::vector<torch::Tensor> masks,
+                                             double inv_keep, torch::ScalarType dtype);
 
 // x[M,K]; per sibling g: W_g[N_g,K], bias_g ([N_g] or empty), A_g[r,K],
 // B_g[N_g,r], scale_g, seed_g, fused_g (use fused_lora_gemm for this one).
@@ -67,11 +73,15 @@ std::vector<torch::Tensor> lora_group_fwd(
 
 // dys[g]: [M,N_g] contiguous.  masks empty (size 0 list) when p == 0.
 // Returns {dx, dA_0.., dB_0..}.
+// group_bwd (RELORA_AMD_LORA_GROUP_BWD): with G >= 2, the LoRA parts of dx go
+// into dx in one lora_add_nn_group_ pass (one read-modify-write of dx, one
+// rounding) and every dA_g comes from one skinny_grad_group launch (x read
+// once).  Off: one lora_add_nn_ and one skinny_grad per sibling.
 std::vector<torch::Tensor> lora_group_bwd(
     std::vector<torch::Tensor> dys, torch::Tensor x, std::vector<torch::Tensor> masks,
     std::vector<torch::Tensor> ts, std::vector<torch::Tensor> Ws,
     std::vector<torch::Tensor> As, std::vector<torch::Tensor> bss,
-    std::vector<double> scales, double p) {
+    std::vector<double> scales, double p, bool group_bwd) {
   const size_t G = dys.size();
   TORCH_CHECK(G >= 1 && G <= 3 && ts.size() == G && Ws.size() == G && As.size() == G &&
               bss.size() == G && scales.size() == G,
@@ -85,12 +95,17 @@ std::vector<torch::Tensor> lora_group_bwd(
   auto dx = at::mm(dys[0], Ws[0]);
   for (size_t g = 1; g < G; ++g) dx.addmm_(dys[g], Ws[g]);
 
-  std::vector<torch::Tensor> dAs, dBs;
+  const bool fuse = group_bwd && G >= 2;
+  std::vector<torch::Tensor> us, dAs, dBs;
   for (size_t g = 0; g < G; ++g) {
     const auto& mask = drop ? masks[g] : empty_mask;
     auto u = at::mm(dys[g], bss[g]);             // [M, r] = s * dy @ B
-    lora_add_nn_(dx, u, As[g], mask, inv_keep);  // dx += mask/(1-p) * (u @ A)
-    dAs.push_back(skinny_grad(u, x, mask, inv_keep, 1.0, false, As[g].scalar_type()));
+    if (fuse) {
+      us.push_back(u);
+    } else {
+      lora_add_nn_(dx, u, As[g], mask, inv_keep);  // dx += mask/(1-p) * (u @ A)
+      dAs.push_back(skinny_grad(u, x, mask, inv_keep, 1.0, false, As[g].scalar_type()));
+    }
     const int64_t N = Ws[g].size(0);
     if (N % 8 == 0) {
       dBs.push_back(skinny_grad(ts[g], dys[g], empty_mask, 1.0, scales[g], true,
@@ -98,6 +113,11 @@ std::vector<torch::Tensor> lora_group_bwd(
     } else {
       dBs.push_back(at::mm(dys[g].t(), ts[g]) * scales[g]);
     }
+  }
+  if (fuse) {
+    if (!drop) masks.clear();
+    lora_add_nn_group_(dx, us, As, masks, inv_keep);  // dx += sum_g mask_g/(1-p) * (u_g @ A_g)
+    dAs = skinny_grad_group(us, x, masks, inv_keep, As[0].scalar_type());
   }
   std::vector<torch::Tensor> out{dx};
   out.insert(out.end(), dAs.begin(), dAs.end());

@@ -900,6 +900,10 @@ def lora_linear(x, weight, bias, lora_A, lora_B, scale, dropout_p=0.0,
 # ---------------------------------------------------------------------------
 
 _LORA_GROUP = os.environ.get("RELORA_AMD_LORA_GROUP", "1") != "0"
+# RELORA_AMD_LORA_GROUP_BWD=0: the group backward calls lora_add_nn_ and
+# skinny_grad once per sibling instead of the two group kernels (dx in one
+# pass, every dA from one read of x).
+_LORA_GROUP_BWD = os.environ.get("RELORA_AMD_LORA_GROUP_BWD", "1") != "0"
 
 
 class _LoRALinearGroup(torch.autograd.Function):
@@ -948,7 +952,8 @@ class _LoRALinearGroup(torch.autograd.Function):
         dy2d = [dy.contiguous().view(-1, W.shape[0]) for dy, W in zip(dys, Ws)]
         out = hip.ext().lora_group_bwd(
             dy2d, x2d, list(masks), list(ts), list(Ws),
-            [A.contiguous() for A in As], list(bss), ctx.scales, p)
+            [A.contiguous() for A in As], list(bss), ctx.scales, p,
+            _LORA_GROUP_BWD)
         dx, dAs, dBs = out[0], out[1:1 + G], out[1 + G:1 + 2 * G]
         grads = []
         for g in range(G):
