@@ -127,20 +127,31 @@ class LlamaAttention(nn.Module):
         bsz, q_len, _ = hidden_states.size()
         if doc_start is not None and past_key_value is not None:
             raise ValueError("doc_start cannot be combined with a kv cache")
-        q, k, v = lora_group_forward(hidden_states, (self.q_proj, self.k_proj, self.v_proj))
+        kv_seq_len = q_len
+        if past_key_value is not None:
+            kv_seq_len += past_key_value[0].shape[-2]
+        cos, sin = self.rotary_emb(hidden_states, seq_len=kv_seq_len)
+        # positions 0..q_len-1 (training, prefill without a cache): q and k come
+        # out of the projection group already rotated — on the group's HIP path
+        # by its LoRA epilogue kernel, elsewhere by ops.rope, the same values
+        rope_in_group = (position_ids is None and past_key_value is None
+                         and cos.shape[0] >= q_len)
+        proj = (self.q_proj, self.k_proj, self.v_proj)
+        if rope_in_group:
+            q, k, v = lora_group_forward(
+                hidden_states, proj, rope=(cos, sin, (True, True, False), self.head_dim))
+        else:
+            q, k, v = lora_group_forward(hidden_states, proj)
         q = q.view(bsz, q_len, self.num_heads, self.head_dim).transpose(1, 2)
         k = k.view(bsz, q_len, self.num_key_value_heads, self.head_dim).transpose(1, 2)
         v = v.view(bsz, q_len, self.num_key_value_heads, self.head_dim).transpose(1, 2)
 
-        kv_seq_len = q_len
-        if past_key_value is not None:
-            kv_seq_len += past_key_value[0].shape[-2]
-        cos, sin = self.rotary_emb(v, seq_len=kv_seq_len)
-        if past_key_value is not None and position_ids is None:
-            position_ids = torch.arange(
-                kv_seq_len - q_len, kv_seq_len, device=hidden_states.device
-            ).unsqueeze(0)
-        q, k = ops.rope(q, k, cos, sin, position_ids=position_ids)
+        if not rope_in_group:
+            if past_key_value is not None and position_ids is None:
+                position_ids = torch.arange(
+                    kv_seq_len - q_len, kv_seq_len, device=hidden_states.device
+                ).unsqueeze(0)
+            q, k = ops.rope(q, k, cos, sin, position_ids=position_ids)
 
         if past_key_value is not None:
             k = torch.cat([past_key_value[0], k], dim=2)

@@ -7,6 +7,7 @@ from relora_amd.ops.functional import (  # noqa: F401
     fused_cross_entropy,
     layernorm,
     lora_group_ok,
+    lora_group_rope_ok,
     lora_linear,
     lora_linear_group,
     add_rmsnorm,

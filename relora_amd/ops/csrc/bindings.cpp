@@ -19,7 +19,7 @@ std::vector<torch::Tensor> layernorm_bwd(torch::Tensor x, torch::Tensor w,
 // rope.hip
 std::vector<torch::Tensor> rope_fwd(torch::Tensor q, torch::Tensor k,
                                     torch::Tensor cos_t, torch::Tensor sin_t,
-                                    bool inverse);
+                                    bool inverse, bool force_scalar);
 // swiglu.hip
 torch::Tensor swiglu_fwd(torch::Tensor g, torch::Tensor u);
 torch::Tensor gelu_fwd(torch::Tensor x);
@@ -51,6 +51,9 @@ torch::Tensor stochastic_round_bf16_op(torch::Tensor x, int64_t seed, long step,
 std::vector<torch::Tensor> dropout_mask_fwd(torch::Tensor x, double p, int64_t seed);
 torch::Tensor dropout_mask_bwd(torch::Tensor dy, torch::Tensor mask, double p);
 void lora_add_nt_(torch::Tensor out, torch::Tensor P, torch::Tensor Q);
+void lora_add_nt_rope_group_(std::vector<torch::Tensor> outs, std::vector<torch::Tensor> Ps,
+                             std::vector<torch::Tensor> Qs, std::vector<int64_t> rotary,
+                             torch::Tensor cos_t, torch::Tensor sin_t, int64_t S, int64_t hd);
 std::vector<torch::Tensor> lora_down_dropout(torch::Tensor x, std::vector<torch::Tensor> As,
                                              std::vector<int64_t> seeds, double p);
 // lora_group.cpp
@@ -58,7 +61,9 @@ std::vector<torch::Tensor> lora_group_fwd(
     torch::Tensor x, std::vector<torch::Tensor> Ws, std::vector<torch::Tensor> biases,
     std::vector<torch::Tensor> As, std::vector<torch::Tensor> Bs,
     std::vector<double> scales, std::vector<int64_t> seeds, double p,
-    std::vector<int64_t> fused);
+    std::vector<int64_t> fused, c10::optional<torch::Tensor> cos_t,
+    c10::optional<torch::Tensor> sin_t, std::vector<int64_t> rotary, int64_t S,
+    int64_t hd);
 std::vector<torch::Tensor> lora_group_bwd(
     std::vector<torch::Tensor> dys, torch::Tensor x, std::vector<torch::Tensor> masks,
     std::vector<torch::Tensor> ts, std::vector<torch::Tensor> Ws,
@@ -108,7 +113,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rmsnorm_bwd_add", &rmsnorm_bwd_add, "RMSNorm bwd with +dsum fused into dx (gfx950)");
   m.def("layernorm_fwd", &layernorm_fwd, "LayerNorm forward (gfx950)");
   m.def("layernorm_bwd", &layernorm_bwd, "LayerNorm backward (gfx950)");
-  m.def("rope_fwd", &rope_fwd, "RoPE apply fwd/inverse (gfx950)");
+  // force_scalar: run the one-pair-per-thread kernel where the vectorised one
+  // would be taken (the tests compare the two)
+  m.def("rope_fwd", &rope_fwd, "RoPE apply fwd/inverse (gfx950)",
+        py::arg("q"), py::arg("k"), py::arg("cos"), py::arg("sin"), py::arg("inverse"),
+        py::arg("force_scalar") = false);
   m.def("swiglu_fwd", &swiglu_fwd, "SwiGLU forward (gfx950)");
   m.def("swiglu_bwd", &swiglu_bwd, "SwiGLU backward (gfx950)");
   m.def("gelu_fwd", &gelu_fwd, "exact-erf GELU forward (gfx950)");
@@ -135,8 +144,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lora_add_nt_", &lora_add_nt_, "out += P @ Q^T rank-r MFMA accumulate (gfx950)");
   m.def("lora_down_dropout", &lora_down_dropout,
         "t_g = dropout_g(x) @ A_g^T for up to 3 siblings, x read once (gfx950)");
+  m.def("lora_add_nt_rope_group_", &lora_add_nt_rope_group_,
+        "out_g += P_g @ Q_g^T for 1..3 siblings in one launch, RoPE applied in place to "
+        "the flagged ones (gfx950)",
+        py::arg("outs"), py::arg("Ps"), py::arg("Qs"), py::arg("rotary"), py::arg("cos"),
+        py::arg("sin"), py::arg("S"), py::arg("hd"));
+  // cos/sin/rotary/S/hd: rotate the flagged siblings in the LoRA epilogue
   m.def("lora_group_fwd", &lora_group_fwd,
-        "group LoRA linear forward for siblings sharing one input (gfx950)");
+        "group LoRA linear forward for siblings sharing one input (gfx950)",
+        py::arg("x"), py::arg("Ws"), py::arg("biases"), py::arg("As"), py::arg("Bs"),
+        py::arg("scales"), py::arg("seeds"), py::arg("p"), py::arg("fused"),
+        py::arg("cos") = py::none(), py::arg("sin") = py::none(),
+        py::arg("rotary") = std::vector<int64_t>(), py::arg("S") = 0, py::arg("hd") = 0);
   m.def("lora_group_bwd", &lora_group_bwd,
         "group LoRA linear backward into one shared dx (gfx950)",
         py::arg("dys"), py::arg("x"), py::arg("masks"), py::arg("ts"), py::arg("Ws"),

@@ -33,6 +33,28 @@ DEV_INLINE void store8(T* p, const Vec8<T>& x) {
   *reinterpret_cast<Vec8<T>*>(p) = x;
 }
 
+// ---- RoPE rotation of one (x1, x2) = (x[i], x[i + R/2]) pair -----------------
+// forward:  y1 = x1*c - x2*s,  y2 = x2*c + x1*s
+// inverse:  y1 = x1*c + x2*s,  y2 = x2*c - x1*s   (the backward rotation)
+// Shared by rope_kernel, rope_vec_kernel (rope.hip) and the fused LoRA + RoPE
+// epilogue (lora_gemm.hip).  Of the two products of each line one is rounded
+// to fp32 and the other fused into the add.  Which one is spelled out, so that
+// every caller rounds alike whatever the compiler would contract on its own;
+// the choice is the one the compiler made for rope_kernel while these lines
+// were written `x1 * c - x2 * s` etc. (read off its ISA), so results did not
+// move when the helper came in.
+
+template <bool INVERSE>
+DEV_INLINE void rope_rotate(float x1, float x2, float c, float s, float& y1, float& y2) {
+  if (INVERSE) {
+    y1 = fmaf(x1, c, __fmul_rn(x2, s));
+    y2 = fmaf(x2, c, -__fmul_rn(x1, s));
+  } else {
+    y1 = fmaf(x1, c, -__fmul_rn(x2, s));
+    y2 = fmaf(x1, s, __fmul_rn(x2, c));
+  }
+}
+
 // ---- block-level reduction (sum) over fp32 --------------------------------
 // One value per thread -> one value broadcast to all threads.
 // Requires blockDim.x <= 1024, caller provides __shared__ float scratch[16].

@@ -18,6 +18,8 @@
 // pad (the attention kernels' proven layout) and read as contiguous-k
 // bf16x8 fragments.
 
+#include <climits>
+
 #include <ATen/hip/HIPContext.h>
 #include <torch/extension.h>
 
@@ -379,6 +381,237 @@ void lora_add_nt_(torch::Tensor out, torch::Tensor P, torch::Tensor Q) {
   hipLaunchKernelGGL((lora_skinny_kernel<false, false>), grid, block, lds, stream,
                      (const __hip_bfloat16*)P.data_ptr(), (const __hip_bfloat16*)Q.data_ptr(),
                      (__hip_bfloat16*)out.data_ptr(), nullptr, 1.f, M, N, r, r);
+  HIP_CHECK_LAST();
+}
+
+// ---------------------------------------------------------------------------
+// Group form of the forward epilogue with RoPE: out_g[M,N_g] += P_g[M,r] @
+// Q_g[N_g,r]^T for G <= 3 siblings (q/k/v) in ONE launch, and for the siblings
+// flagged rotary the rotation is applied to the summed tile before it is
+// stored — the separate rope pass over q and k (read y, write a new tensor)
+// disappears.
+//
+// Same 128x128 tile, staging, MFMA loop and bf16 [128][136] LDS out tile as
+// lora_skinny_kernel<false,false>.  The siblings share nothing (P_g, Q_g and
+// out_g all differ), so the grid is flat over the concatenated column tiles of
+// all siblings: blockIdx.x -> (sibling, column tile); a loop over siblings
+// inside the block would reuse no operand and only cut the block count by G.
+//
+// Epilogue: a thread owns 4 (row, 8-column group) pairs: group c in the first
+// half of a head and its partner c + hd/2; with hd 64 or 128 and N_g % 128 == 0
+// both lie in this tile.  The two bf16x8 of out are loaded before the staging
+// and MFMA work (8 loads in flight under it), the update is added and rounded
+// to bf16 exactly as lora_add_nt_ does, and the rotation works on those bf16
+// values with rope_rotate (common.h): the stored bits equal lora_add_nt_
+// followed by rope_fwd.  Non-rotary siblings (v) skip the rotation only.
+// The position of row m is m % S (out_g is [B*S, N_g]); cos/sin are the fp32
+// [S_cache, hd] tables of rope.hip (R == hd).
+// ---------------------------------------------------------------------------
+
+struct LoraRopeGroupArgs {
+  const __hip_bfloat16* P[3];
+  const __hip_bfloat16* Q[3];
+  __hip_bfloat16* out[3];
+  int N[3];
+  int tile0[3];   // first flat column tile of sibling g (INT_MAX when g >= G)
+  int rotary[3];
+};
+
+__global__ __launch_bounds__(256, 2) void lora_skinny_rope_group_kernel(
+    LoraRopeGroupArgs a, const float* __restrict__ cos_t, const float* __restrict__ sin_t,
+    long M, int r, int S, int hd) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int ldt = r + LPAD;
+  __bf16* p_im = (__bf16*)smem;       // [128][ldt]
+  __bf16* q_im = p_im + 128 * ldt;    // [128][ldt]
+
+  // sibling and column tile of this block (selects, not indexing: the
+  // argument struct stays in scalar registers)
+  const int bx = blockIdx.x;
+  const int g = bx >= a.tile0[2] ? 2 : (bx >= a.tile0[1] ? 1 : 0);
+  const __hip_bfloat16* P = g == 0 ? a.P[0] : (g == 1 ? a.P[1] : a.P[2]);
+  const __hip_bfloat16* Q = g == 0 ? a.Q[0] : (g == 1 ? a.Q[1] : a.Q[2]);
+  __hip_bfloat16* out = g == 0 ? a.out[0] : (g == 1 ? a.out[1] : a.out[2]);
+  const int N = g == 0 ? a.N[0] : (g == 1 ? a.N[1] : a.N[2]);
+  const int tile0 = g == 0 ? a.tile0[0] : (g == 1 ? a.tile0[1] : a.tile0[2]);
+  const bool rotary = (g == 0 ? a.rotary[0] : (g == 1 ? a.rotary[1] : a.rotary[2])) != 0;
+
+  const long m0 = (long)blockIdx.y * 128;
+  const int n0 = (bx - tile0) * 128;
+  const int mrem = (int)min(M - m0, 128L);  // valid rows of the tile
+
+  // this thread's pairs: rows prow + 32 i, columns c .. c+7 and c+half .. +7
+  const int prow = threadIdx.x >> 3;
+  const int u = threadIdx.x & 7;
+  const int half = hd >> 1;
+  const int hg = hd >> 4;              // 8-column groups per half head: 4 or 8
+  const int ci = (u & (hg - 1)) * 8;   // column inside the half head
+  const int c = (u / hg) * hd + ci;
+  __hip_bfloat16* obase = out + m0 * (long)N + n0 + c;
+  Vec8<__hip_bfloat16> y1[4], y2[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int row = prow + i * 32;
+    if (row < mrem) {
+      y1[i] = load8(obase + (long)row * N);
+      y2[i] = load8(obase + (long)row * N + half);
+    }
+  }
+
+  // stage P rows [128][r] and the Q tile as q_im[n][k]
+  for (int t = threadIdx.x; t < 128 * (r / 8); t += blockDim.x) {
+    const int row = t / (r / 8);
+    const int k8 = (t % (r / 8)) * 8;
+    bf16x8 v;
+    if (row < mrem) {
+      v = *reinterpret_cast<const bf16x8*>(P + (m0 + row) * (long)r + k8);
+    } else {
+      v = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+    }
+    *reinterpret_cast<bf16x8*>(p_im + rm_idx(row, k8, ldt)) = v;
+  }
+  for (int t = threadIdx.x; t < 128 * (r / 8); t += blockDim.x) {
+    const int n = t / (r / 8);
+    const int k8 = (t % (r / 8)) * 8;
+    // N % 128 == 0: every row of the tile exists
+    *reinterpret_cast<bf16x8*>(q_im + rm_idx(n, k8, ldt)) =
+        *reinterpret_cast<const bf16x8*>(Q + (n0 + n) * (long)r + k8);
+  }
+  __syncthreads();
+
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int wr = (wave >> 1) * 64;  // wave row offset in tile
+  const int wc = (wave & 1) * 64;   // wave col offset
+  const int fr = lane & 15;         // fragment row/col
+  const int kg = (lane >> 4) * 8;   // k-group offset
+
+  f32x4 acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  for (int kk = 0; kk < r; kk += 32) {
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi) {
+      const bf16x8 av =
+          *reinterpret_cast<const bf16x8*>(p_im + rm_idx(wr + mi * 16 + fr, kk + kg, ldt));
+#pragma unroll
+      for (int ni = 0; ni < 4; ++ni) {
+        const bf16x8 bv = *reinterpret_cast<const bf16x8*>(
+            q_im + rm_idx(wc + ni * 16 + fr, kk + kg, ldt));
+        acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, bv, acc[mi][ni], 0, 0, 0);
+      }
+    }
+  }
+
+  __syncthreads();  // done with p_im/q_im; reuse the LDS as the out tile
+  __bf16* o_im = (__bf16*)smem;  // [128][OLD]
+  constexpr int OLD = 128 + LPAD;
+  const int crow = (lane >> 4) * 4;  // C-frag rows crow..crow+3, col = fr
+#pragma unroll
+  for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < 4; ++ni)
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        o_im[rm_idx(wr + mi * 16 + crow + j, wc + ni * 16 + fr, OLD)] =
+            (__bf16)acc[mi][ni][j];
+  __syncthreads();
+
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int row = prow + i * 32;
+    if (row >= mrem) continue;
+    const bf16x8 u1 = *reinterpret_cast<const bf16x8*>(o_im + rm_idx(row, c, OLD));
+    const bf16x8 u2 = *reinterpret_cast<const bf16x8*>(o_im + rm_idx(row, c + half, OLD));
+    Vec8<__hip_bfloat16> o1, o2;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      o1.v[j] = from_f32<__hip_bfloat16>(to_f32(y1[i].v[j]) + (float)u1[j]);
+      o2.v[j] = from_f32<__hip_bfloat16>(to_f32(y2[i].v[j]) + (float)u2[j]);
+    }
+    if (rotary) {
+      const long s = (m0 + row) % S;
+      const Vec8<float> cs = load8(cos_t + s * hd + ci);
+      const Vec8<float> sn = load8(sin_t + s * hd + ci);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        float r1, r2;
+        rope_rotate<false>(to_f32(o1.v[j]), to_f32(o2.v[j]), cs.v[j], sn.v[j], r1, r2);
+        o1.v[j] = from_f32<__hip_bfloat16>(r1);
+        o2.v[j] = from_f32<__hip_bfloat16>(r2);
+      }
+    }
+    store8(obase + (long)row * N, o1);
+    store8(obase + (long)row * N + half, o2);
+  }
+}
+
+// outs[g][M,N_g] += Ps[g][M,r] @ Qs[g][N_g,r]^T for G = 1..3 siblings in one
+// launch; siblings with rotary[g] != 0 are RoPE-rotated in place (heads of hd
+// columns, position of row m = m % S, cos/sin fp32 [S_cache, hd]).
+void lora_add_nt_rope_group_(std::vector<torch::Tensor> outs, std::vector<torch::Tensor> Ps,
+                             std::vector<torch::Tensor> Qs, std::vector<int64_t> rotary,
+                             torch::Tensor cos_t, torch::Tensor sin_t, int64_t S,
+                             int64_t hd) {
+  const int G = (int)outs.size();
+  TORCH_CHECK(G >= 1 && G <= 3 && (int)Ps.size() == G && (int)Qs.size() == G &&
+              (int)rotary.size() == G,
+              "lora_add_nt_rope_group_: 1..3 siblings, one P, Q and flag per out");
+  TORCH_CHECK(hd == 64 || hd == 128, "lora_add_nt_rope_group_: head_dim must be 64 or 128");
+  TORCH_CHECK(cos_t.is_cuda() && sin_t.is_cuda() && cos_t.dim() == 2 &&
+              cos_t.scalar_type() == torch::kFloat32 &&
+              sin_t.scalar_type() == torch::kFloat32 && cos_t.is_contiguous() &&
+              sin_t.is_contiguous() && sin_t.sizes() == cos_t.sizes() &&
+              ((uintptr_t)cos_t.data_ptr() & 15) == 0 && ((uintptr_t)sin_t.data_ptr() & 15) == 0,
+              "lora_add_nt_rope_group_: cos/sin must be contiguous fp32 [S_cache, hd]");
+  TORCH_CHECK(cos_t.size(1) == hd, "lora_add_nt_rope_group_: full rotary only (R == head_dim)");
+  TORCH_CHECK(S >= 1 && cos_t.size(0) >= S, "rope cache shorter than sequence");
+  TORCH_CHECK(Ps[0].dim() == 2, "lora_add_nt_rope_group_: P_g must be [M,r]");
+  const long M = Ps[0].size(0);
+  const int r = Ps[0].size(1);
+  TORCH_CHECK(r % 32 == 0 && r <= 128,
+              "lora_add_nt_rope_group_: r must be a multiple of 32, <= 128");
+  LoraRopeGroupArgs a = {};
+  int tiles = 0;
+  for (int g = 0; g < 3; ++g) a.tile0[g] = INT_MAX;
+  for (int g = 0; g < G; ++g) {
+    const auto& out = outs[g];
+    const auto& P = Ps[g];
+    const auto& Q = Qs[g];
+    TORCH_CHECK(out.is_cuda() && P.is_cuda() && Q.is_cuda() && out.is_contiguous() &&
+                P.is_contiguous() && Q.is_contiguous() &&
+                out.scalar_type() == torch::kBFloat16 &&
+                P.scalar_type() == torch::kBFloat16 && Q.scalar_type() == torch::kBFloat16,
+                "lora_add_nt_rope_group_: out_g, P_g, Q_g must be contiguous bf16");
+    TORCH_CHECK(out.dim() == 2 && P.dim() == 2 && Q.dim() == 2 && out.size(0) == M &&
+                P.size(0) == M && P.size(1) == r && Q.size(1) == r &&
+                Q.size(0) == out.size(1),
+                "lora_add_nt_rope_group_: shape mismatch");
+    const long N = out.size(1);
+    TORCH_CHECK(N % 128 == 0 && N % hd == 0 && N < (1L << 24),
+                "lora_add_nt_rope_group_: N_g must be a multiple of 128");
+    TORCH_CHECK(((uintptr_t)out.data_ptr() & 15) == 0 && ((uintptr_t)P.data_ptr() & 15) == 0 &&
+                ((uintptr_t)Q.data_ptr() & 15) == 0,
+                "lora_add_nt_rope_group_: 16-byte aligned tensors only");
+    a.out[g] = (__hip_bfloat16*)out.data_ptr();
+    a.P[g] = (const __hip_bfloat16*)P.data_ptr();
+    a.Q[g] = (const __hip_bfloat16*)Q.data_ptr();
+    a.N[g] = (int)N;
+    a.rotary[g] = rotary[g] != 0;
+    a.tile0[g] = tiles;
+    tiles += (int)(N / 128);
+  }
+  if (M == 0) return;
+  TORCH_CHECK((M + 127) / 128 <= 65535, "lora_add_nt_rope_group_: too many rows");
+  auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
+  const size_t lds = std::max<size_t>(2u * 128 * (r + LPAD), 128u * (128 + LPAD))
+                     * sizeof(__bf16);
+  dim3 grid(tiles, (M + 127) / 128), block(256);
+  hipLaunchKernelGGL(lora_skinny_rope_group_kernel, grid, block, lds, stream, a,
+                     cos_t.data_ptr<float>(), sin_t.data_ptr<float>(), M, r, (int)S, (int)hd);
   HIP_CHECK_LAST();
 }
 

@@ -15,6 +15,9 @@
 std::vector<torch::Tensor> lora_down_dropout(torch::Tensor x, std::vector<torch::Tensor> As,
                                              std::vector<int64_t> seeds, double p);
 void lora_add_nt_(torch::Tensor out, torch::Tensor P, torch::Tensor Q);
+void lora_add_nt_rope_group_(std::vector<torch::Tensor> outs, std::vector<torch::Tensor> Ps,
+                             std::vector<torch::Tensor> Qs, std::vector<int64_t> rotary,
+                             torch::Tensor cos_t, torch::Tensor sin_t, int64_t S, int64_t hd);
 void lora_add_nn_(torch::Tensor out, torch::Tensor P, torch::Tensor Q,
                   torch::Tensor mask, double inv_keep);
 torch::Tensor fused_lora_gemm(torch::Tensor x, torch::Tensor w, torch::Tensor t,
@@ -33,15 +36,31 @@ std::vector<torch::Tensor> skinny_grad_group(std::vector<torch::Tensor> Ps, torc
 // B_g[N_g,r], scale_g, seed_g, fused_g (use fused_lora_gemm for this one).
 // Returns 4 tensors per sibling, grouped: {y_0..}, {t_0..}, {bs_0..},
 // {mask_0..} (masks only when p > 0), with bs_g = scale_g * B_g.
+//
+// With cos/sin given (fp32 [S_cache, hd] tables; x is [B*S, K], row m sits at
+// position m % S), the siblings flagged in `rotary` come back RoPE-rotated:
+// the G lora_add_nt_ launches and the separate rope pass become one
+// lora_add_nt_rope_group_ launch.  The caller asks for this only where that
+// kernel's constraints hold (ops/functional.py: lora_group_rope_ok); anything
+// else is an error here, not a fall-back.
 std::vector<torch::Tensor> lora_group_fwd(
     torch::Tensor x, std::vector<torch::Tensor> Ws, std::vector<torch::Tensor> biases,
     std::vector<torch::Tensor> As, std::vector<torch::Tensor> Bs,
     std::vector<double> scales, std::vector<int64_t> seeds, double p,
-    std::vector<int64_t> fused) {
+    std::vector<int64_t> fused, c10::optional<torch::Tensor> cos_t,
+    c10::optional<torch::Tensor> sin_t, std::vector<int64_t> rotary, int64_t S,
+    int64_t hd) {
   const size_t G = Ws.size();
   TORCH_CHECK(G >= 1 && G <= 3 && biases.size() == G && As.size() == G &&
               Bs.size() == G && scales.size() == G && fused.size() == G,
               "lora_group_fwd: per-sibling lists must have 1..3 entries each");
+  const bool rope = cos_t.has_value();
+  if (rope) {
+    TORCH_CHECK(sin_t.has_value() && rotary.size() == G,
+                "lora_group_fwd: rope needs cos, sin and one rotary flag per sibling");
+    for (size_t g = 0; g < G; ++g)
+      TORCH_CHECK(!fused[g], "lora_group_fwd: rope cannot follow fused_lora_gemm siblings");
+  }
   auto tm = lora_down_dropout(x, As, seeds, p);  // {t_0.., mask_0..}
   std::vector<torch::Tensor> ys, bss;
   for (size_t g = 0; g < G; ++g) {
@@ -55,7 +74,9 @@ std::vector<torch::Tensor> lora_group_fwd(
                           has_bias ? biases[g] : x.new_empty({0}), scales[g]);
     } else {
       y = has_bias ? at::linear(x, Ws[g], biases[g]) : at::linear(x, Ws[g]);
-      if (N % 8 == 0) {
+      if (rope) {
+        // added (and rotated) below, all siblings in one launch
+      } else if (N % 8 == 0) {
         lora_add_nt_(y, t, bs);                  // y += t @ bs^T
       } else {
         y.addmm_(t, bs.t());                     // library, beta = 1
@@ -63,6 +84,10 @@ std::vector<torch::Tensor> lora_group_fwd(
     }
     ys.push_back(y);
     bss.push_back(bs);
+  }
+  if (rope) {
+    std::vector<torch::Tensor> ts(tm.begin(), tm.begin() + G);
+    lora_add_nt_rope_group_(ys, ts, bss, rotary, *cos_t, *sin_t, S, hd);
   }
   std::vector<torch::Tensor> out(ys);
   out.insert(out.end(), tm.begin(), tm.begin() + G);

@@ -904,14 +904,23 @@ _LORA_GROUP = os.environ.get("RELORA_AMD_LORA_GROUP", "1") != "0"
 # skinny_grad once per sibling instead of the two group kernels (dx in one
 # pass, every dA from one read of x).
 _LORA_GROUP_BWD = os.environ.get("RELORA_AMD_LORA_GROUP_BWD", "1") != "0"
+# RELORA_AMD_LORA_GROUP_ROPE=0: q and k leave the group op unrotated and
+# ops.rope runs on them afterwards (one lora_add_nt_ per sibling, then the
+# rope kernel) instead of the rotation in the group's LoRA epilogue.
+_LORA_GROUP_ROPE = os.environ.get("RELORA_AMD_LORA_GROUP_ROPE", "1") != "0"
 
 
 class _LoRALinearGroup(torch.autograd.Function):
     """`tensors` is (weight, bias-or-None, lora_A, lora_B) per sibling,
-    flattened; returns one output per sibling."""
+    flattened; returns one output per sibling.
+
+    `rope` is None or (cos, sin, flags, head_dim), fp32 contiguous tables:
+    the outputs of the flagged siblings come back RoPE-rotated (position =
+    index along x's second-to-last dim), the rotation done by the LoRA
+    epilogue kernel.  Callers check `lora_group_rope_ok` first."""
 
     @staticmethod
-    def forward(ctx, x, scales, dropout_p, training, *tensors):
+    def forward(ctx, x, scales, dropout_p, training, rope, *tensors):
         G = len(scales)
         Ws, biases = tensors[0::4], tensors[1::4]
         As, Bs = tensors[2::4], tensors[3::4]
@@ -925,14 +934,20 @@ class _LoRALinearGroup(torch.autograd.Function):
                  if use_dropout else [])
         empty = x2d.new_empty(0)
         fused = [int(_use_fused_k1(x2d, W, A)) for W, A in zip(Ws, As)]
+        rope_args, tables = (), ()
+        if rope is not None:
+            cos, sin, flags, head_dim = rope
+            tables = (cos, sin)
+            rope_args = (cos, sin, [int(bool(f)) for f in flags], in_shape[-2], head_dim)
         out = hip.ext().lora_group_fwd(
             x2d, list(Ws), [b if b is not None else empty for b in biases],
             [A.contiguous() for A in As], [B.contiguous() for B in Bs],
             [float(s) for s in scales],
-            seeds, dropout_p if use_dropout else 0.0, fused)
+            seeds, dropout_p if use_dropout else 0.0, fused, *rope_args)
         ys, ts, bss = out[:G], out[G:2 * G], out[2 * G:3 * G]
         masks = out[3 * G:]
-        ctx.save_for_backward(x2d, *ts, *bss, *masks, *Ws, *As)
+        ctx.save_for_backward(x2d, *ts, *bss, *masks, *Ws, *As, *tables)
+        ctx.rope = None if rope is None else (rope_args[2], rope_args[3], rope_args[4])
         ctx.G = G
         ctx.scales = [float(s) for s in scales]
         ctx.dropout_p = dropout_p if use_dropout else 0.0
@@ -950,6 +965,21 @@ class _LoRALinearGroup(torch.autograd.Function):
         Ws = saved[1 + 2 * G + nm:1 + 3 * G + nm]
         As = saved[1 + 3 * G + nm:1 + 4 * G + nm]
         dy2d = [dy.contiguous().view(-1, W.shape[0]) for dy, W in zip(dys, Ws)]
+        if ctx.rope is not None:
+            # undo the rotation on the gradients of the rotated outputs, out
+            # of place (an incoming gradient may be shared), q and k in one
+            # launch; from here on backward is that of the unrotated op
+            cos, sin = saved[1 + 4 * G + nm:3 + 4 * G + nm]
+            flags, S, hd = ctx.rope
+            rot = [g for g in range(G) if flags[g]]
+            for i in range(0, len(rot), 2):
+                pair = [dy2d[g].view(-1, S, dy2d[g].shape[1] // hd, hd).transpose(1, 2)
+                        for g in rot[i:i + 2]]
+                if len(pair) == 1:  # no partner: a tensor without heads
+                    pair.append(pair[0].new_empty(pair[0].shape[0], 0, S, hd))
+                res = hip.ext().rope_fwd(pair[0], pair[1], cos, sin, True)
+                for g, d in zip(rot[i:i + 2], res):
+                    dy2d[g] = d.transpose(1, 2).reshape(-1, dy2d[g].shape[1])
         out = hip.ext().lora_group_bwd(
             dy2d, x2d, list(masks), list(ts), list(Ws),
             [A.contiguous() for A in As], list(bss), ctx.scales, p,
@@ -957,12 +987,12 @@ class _LoRALinearGroup(torch.autograd.Function):
         dx, dAs, dBs = out[0], out[1:1 + G], out[1 + G:1 + 2 * G]
         grads = []
         for g in range(G):
-            # needs_input_grad index: 4 leading non-sibling args, 4 per sibling
-            dw = dy2d[g].t() @ x2d if ctx.needs_input_grad[4 + 4 * g] else None
+            # needs_input_grad index: 5 leading non-sibling args, 4 per sibling
+            dw = dy2d[g].t() @ x2d if ctx.needs_input_grad[5 + 4 * g] else None
             dbias = (dy2d[g].sum(0)
-                     if ctx.has_bias[g] and ctx.needs_input_grad[5 + 4 * g] else None)
+                     if ctx.has_bias[g] and ctx.needs_input_grad[6 + 4 * g] else None)
             grads += [dw, dbias, dAs[g], dBs[g]]
-        return (dx.view(dys[0].shape[:-1] + (x2d.shape[1],)), None, None, None,
+        return (dx.view(dys[0].shape[:-1] + (x2d.shape[1],)), None, None, None, None,
                 *grads)
 
 
@@ -993,12 +1023,44 @@ def lora_group_ok(x, specs):
     return True
 
 
-def lora_linear_group(x, specs, dropout_p=0.0, training=False):
+def lora_group_rope_ok(x, specs, rope):
+    """Whether the group op can rotate the flagged outputs in its LoRA
+    epilogue (lora_add_nt_rope_group_), given that `lora_group_ok(x, specs)`
+    holds.  `rope` is (cos, sin, flags, head_dim).  The kernel takes full
+    rotary over heads of 64 or 128 columns, N % 128 == 0 for every sibling,
+    x of shape [..., S, K] with S inside the tables, and fp32 contiguous
+    tables; a group with a sibling that the single-linear rule routes to
+    fused_lora_gemm (K <= 1024) keeps the separate rope pass, as does
+    RELORA_AMD_LORA_GROUP_ROPE=0."""
+    cos, sin, flags, hd = rope
+    if not (_LORA_GROUP_ROPE and x.dim() >= 2 and len(flags) == len(specs) and any(flags)):
+        return False
+    if hd not in (64, 128) or cos.dim() != 2 or cos.shape != sin.shape:
+        return False
+    if cos.shape[1] != hd or cos.shape[0] < x.shape[-2]:
+        return False
+    if not all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+               and t.data_ptr() % 16 == 0 for t in (cos, sin)):
+        return False
+    x2d = x.view(-1, x.shape[-1]) if x.is_contiguous() else x.reshape(-1, x.shape[-1])
+    for weight, _, lora_A, _, _ in specs:
+        if weight.shape[0] % 128 != 0 or weight.shape[0] % hd != 0:
+            return False
+        if _use_fused_k1(x2d, weight, lora_A):
+            return False
+    return True
+
+
+def lora_linear_group(x, specs, dropout_p=0.0, training=False, rope=None):
     """[lora_linear(x, *spec) for spec in specs] for siblings that share the
     input `x`, as one group op.  `specs` is a list of (weight, bias, lora_A,
-    lora_B, scale); callers check `lora_group_ok` first."""
+    lora_B, scale); callers check `lora_group_ok` first.  With `rope` =
+    (cos, sin, flags, head_dim) the flagged outputs come back rotated;
+    callers check `lora_group_rope_ok` too."""
     flat = []
     for weight, bias, lora_A, lora_B, _ in specs:
         flat += [weight, bias, lora_A, lora_B]
+    if rope is not None:
+        rope = (rope[0], rope[1], tuple(bool(f) for f in rope[2]), int(rope[3]))
     return list(_LoRALinearGroup.apply(
-        x, tuple(float(s[4]) for s in specs), dropout_p, training, *flat))
+        x, tuple(float(s[4]) for s in specs), dropout_p, training, rope, *flat))

@@ -338,7 +338,24 @@ class ReLoRaLinear(nn.Module):
                 f"r={self.r}, lora_alpha={self.lora_alpha}")
 
 
-def lora_group_forward(x, modules):
+def _rope_outputs(ys, rope):
+    """ops.rope on the flagged [B, S, N] outputs (heads of head_dim columns),
+    two at a time; the others pass through."""
+    cos, sin, flags, hd = rope
+    ys = list(ys)
+    rot = [g for g, f in enumerate(flags) if f]
+    for i in range(0, len(rot), 2):
+        pair = [ys[g].view(*ys[g].shape[:-1], ys[g].shape[-1] // hd, hd).transpose(-3, -2)
+                for g in rot[i:i + 2]]
+        if len(pair) == 1:  # no partner: a tensor without heads
+            pair.append(pair[0][..., :0, :, :])
+        res = ops.rope(pair[0], pair[1], cos, sin)
+        for g, y in zip(rot[i:i + 2], res):
+            ys[g] = y.transpose(-3, -2).reshape(ys[g].shape)
+    return ys
+
+
+def lora_group_forward(x, modules, rope=None):
     """[m(x) for m in modules] for sibling projections that share the input
     `x` (q/k/v, gate/up).  When every module is a plain (not quantized, not
     lora_only, float-scale) ReLoRaLinear with the same r and dropout p and
@@ -346,8 +363,22 @@ def lora_group_forward(x, modules):
     (`ops.lora_linear_group`): one dropout + down-projection pass over x for
     all of them and one shared input-gradient buffer in backward.  Anything
     else — CPU, fp32, hooks registered on a module, RELORA_AMD_LORA_GROUP=0 —
-    calls the modules one by one, exactly as before."""
+    calls the modules one by one, exactly as before.
+
+    `rope` = (cos, sin, flags, head_dim), with x of shape [B, S, K]: the
+    outputs whose flag is set come back RoPE-rotated at positions 0..S-1
+    (heads of head_dim columns; the caller still views them as heads).  Where
+    the group op can, it rotates in its LoRA epilogue kernel
+    (`ops.lora_group_rope_ok`); everywhere else `ops.rope` runs on the flagged
+    outputs afterwards.  The result is the same either way."""
     modules = list(modules)
+    if rope is not None:
+        cos, sin, flags, hd = rope
+        if x.is_cuda:  # the kernels' contract: fp32 contiguous tables
+            cos, sin = cos.float().contiguous(), sin.float().contiguous()
+        rope = (cos, sin, tuple(bool(f) for f in flags), hd)
+        if x.dim() != 3 or len(rope[2]) != len(modules):
+            raise ValueError("rope needs x of shape [B, S, K] and one flag per module")
     first = modules[0]
     groupable = x.is_cuda and all(
         isinstance(m, ReLoRaLinear) and m.quantize is None and not m.lora_only
@@ -360,6 +391,11 @@ def lora_group_forward(x, modules):
         specs = [(m.weight, m.bias, m.lora_A.weight, m.lora_B.weight,
                   m._post_lora_scale()) for m in modules]
         if ops.lora_group_ok(x, specs):
-            return ops.lora_linear_group(x, specs, dropout_p=first.lora_dropout_p,
-                                         training=first.training)
-    return [m(x) for m in modules]
+            if rope is not None and ops.lora_group_rope_ok(x, specs, rope):
+                return ops.lora_linear_group(x, specs, dropout_p=first.lora_dropout_p,
+                                             training=first.training, rope=rope)
+            ys = ops.lora_linear_group(x, specs, dropout_p=first.lora_dropout_p,
+                                       training=first.training)
+            return ys if rope is None else _rope_outputs(ys, rope)
+    ys = [m(x) for m in modules]
+    return ys if rope is None else _rope_outputs(ys, rope)
