@@ -31,6 +31,80 @@
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_g;
 typedef __attribute__((ext_vector_type(4))) float f32x4_g;
 
+// ---------------------------------------------------------------------------
+// Host checks shared by the five entry points.  The kernels index every
+// operand from M, N, K and r alone, so whatever is not checked here is read
+// out of bounds on a mismatch.  All of them run before the launch.
+// ---------------------------------------------------------------------------
+
+static void check_x(const char* fn, const torch::Tensor& x) {
+  TORCH_CHECK(x.is_cuda(), fn, ": x must be a GPU tensor");
+  TORCH_CHECK(x.dim() == 2, fn, ": x must be 2-D [M, K]");
+  TORCH_CHECK(x.is_contiguous(), fn, ": x must be contiguous");
+  TORCH_CHECK(x.scalar_type() == torch::kBFloat16, fn, ": x must be bf16");
+  TORCH_CHECK(x.size(0) > 0, fn, ": M must be > 0");
+  TORCH_CHECK(x.size(1) > 0, fn, ": K must be > 0");
+}
+
+static void check_dense_w(const char* fn, const torch::Tensor& x,
+                          const torch::Tensor& w) {
+  TORCH_CHECK(w.is_cuda() && w.device() == x.device(), fn,
+              ": w must be on x's device");
+  TORCH_CHECK(w.dim() == 2, fn, ": w must be 2-D [N, K]");
+  TORCH_CHECK(w.is_contiguous(), fn, ": w must be contiguous");
+  TORCH_CHECK(w.scalar_type() == torch::kBFloat16, fn, ": w must be bf16");
+  TORCH_CHECK(w.size(1) == x.size(1), fn, ": K mismatch between x and w");
+  TORCH_CHECK(w.size(0) > 0, fn, ": N must be > 0");
+}
+
+// qw holds `qw_numel` codes bytes, amax one fp32 per `block` weights
+static void check_quant_w(const char* fn, const torch::Tensor& x,
+                          const torch::Tensor& qw, const torch::Tensor& amax,
+                          long N, long K, long qw_numel, long block) {
+  TORCH_CHECK(N > 0, fn, ": N must be > 0");
+  TORCH_CHECK(qw.device() == x.device(), fn, ": qw must be on x's device");
+  TORCH_CHECK(qw.is_contiguous(), fn, ": qw must be contiguous");
+  TORCH_CHECK(qw.numel() == qw_numel, fn, ": packed weight size mismatch");
+  TORCH_CHECK(amax.device() == x.device(), fn, ": absmax must be on x's device");
+  TORCH_CHECK(amax.scalar_type() == torch::kFloat32, fn, ": absmax must be fp32");
+  TORCH_CHECK(amax.is_contiguous(), fn, ": absmax must be contiguous");
+  TORCH_CHECK(amax.numel() == N * K / block, fn,
+              ": absmax must hold N*K/", block, " values");
+}
+
+// Returns r (0 without LoRA).  Runs before the lora_scale == 1.0 shortcut
+// that hands `t` to the kernel as it came.
+static int check_lora(const char* fn, const torch::Tensor& x,
+                      const torch::Tensor& t, const torch::Tensor& bw,
+                      long M, long N, int r_step, int r_max) {
+  if (!(t.defined() && t.numel() > 0)) return 0;
+  TORCH_CHECK(t.device() == x.device(), fn, ": t must be on x's device");
+  TORCH_CHECK(t.scalar_type() == torch::kBFloat16, fn, ": t must be bf16");
+  TORCH_CHECK(t.is_contiguous(), fn, ": t must be contiguous");
+  TORCH_CHECK(t.dim() == 2 && t.size(0) == M, fn, ": t must be [M, r]");
+  const long r = t.size(1);
+  TORCH_CHECK(r % r_step == 0 && r <= r_max, fn, ": r must be a multiple of ",
+              r_step, ", <= ", r_max);
+  TORCH_CHECK(bw.defined() && bw.device() == x.device(), fn,
+              ": bw must be on x's device");
+  TORCH_CHECK(bw.scalar_type() == torch::kBFloat16, fn, ": bw must be bf16");
+  TORCH_CHECK(bw.is_contiguous(), fn, ": bw must be contiguous");
+  TORCH_CHECK(bw.dim() == 2 && bw.size(0) == N && bw.size(1) == r, fn,
+              ": bw must be [N, r]");
+  return (int)r;
+}
+
+// Returns the bias pointer, or null for an undefined / empty bias.
+static const __hip_bfloat16* check_bias(const char* fn, const torch::Tensor& x,
+                                        const torch::Tensor& bias, long N) {
+  if (!(bias.defined() && bias.numel() > 0)) return nullptr;
+  TORCH_CHECK(bias.device() == x.device(), fn, ": bias must be on x's device");
+  TORCH_CHECK(bias.scalar_type() == torch::kBFloat16, fn, ": bias must be bf16");
+  TORCH_CHECK(bias.is_contiguous(), fn, ": bias must be contiguous");
+  TORCH_CHECK(bias.numel() == N, fn, ": bias must have N elements");
+  return (const __hip_bfloat16*)bias.data_ptr();
+}
+
 // st_16x32 swizzle on a byte offset within a [rows][64] bf16 image
 // (128-B rows): byte bit5 ^= bit9 — spreads each ds_read_b128 lane group
 // over four 16-B slots (guide: bank-conflict 141x down, +35%).
@@ -585,7 +659,10 @@ DEV_INLINE void stage_tile_int8(__bf16* image, const int8_t* qdata,
   const int row = tid >> 1;
   const int half = tid & 1;
   const long flat = (row0 + row) * K + k0 + half * 32;
-  const float sc = absmax[flat >> 8] * (1.f / 127.f);
+  // absmax / 127, as dequantize_int8 spells it: absmax * (1/127) differs by
+  // an fp32 ulp for some blocks, and the forward would then see another W
+  // than the backward's materialized one wherever that crosses a bf16 tie
+  const float sc = absmax[flat >> 8] / 127.f;
   union { uint32_t u[8]; int8_t b[32]; } pk;
   *reinterpret_cast<uint4*>(pk.u) = *reinterpret_cast<const uint4*>(qdata + flat);
   *reinterpret_cast<uint4*>(pk.u + 4) = *reinterpret_cast<const uint4*>(qdata + flat + 16);
@@ -718,20 +795,19 @@ __global__ __launch_bounds__(512) void fused_int8_gemm_kernel(
 torch::Tensor fused_int8_gemm(torch::Tensor x, torch::Tensor qw, torch::Tensor amax,
                               long N, torch::Tensor t, torch::Tensor bw,
                               torch::Tensor bias, double lora_scale) {
-  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.is_contiguous());
-  TORCH_CHECK(qw.scalar_type() == torch::kInt8 || qw.scalar_type() == torch::kChar);
+  const char* fn = "fused_int8_gemm";
+  check_x(fn, x);
+  TORCH_CHECK(qw.scalar_type() == torch::kInt8, fn, ": qw must be int8");
   const long M = x.size(0), K = x.size(1);
-  TORCH_CHECK(qw.numel() == N * K, "packed int8 size mismatch");
   TORCH_CHECK(M % 256 == 0 && N % 256 == 0 && K % 256 == 0,
               "fused_int8_gemm requires M%256==0, N%256==0, K%256==0");
-  int r = 0;
-  const bool has_lora = t.defined() && t.numel() > 0;
+  check_quant_w(fn, x, qw, amax, N, K, N * K, 256);
+  const int r = check_lora(fn, x, t, bw, M, N, 64, 256);
+  const bool has_lora = r > 0;
+  const __hip_bfloat16* bias_p = check_bias(fn, x, bias, N);
   torch::Tensor t_scaled;
-  if (has_lora) {
-    r = (int)t.size(1);
-    TORCH_CHECK(r % 64 == 0 && r <= 256);
+  if (has_lora)
     t_scaled = (lora_scale == 1.0) ? t : (t * lora_scale).contiguous();
-  }
   auto y = torch::empty({M, N}, x.options());
   auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
   dim3 grid((M >> 8) * (N >> 8));
@@ -742,9 +818,8 @@ torch::Tensor fused_int8_gemm(torch::Tensor x, torch::Tensor qw, torch::Tensor a
                      amax.data_ptr<float>(),
                      has_lora ? (const __hip_bfloat16*)t_scaled.data_ptr() : nullptr,
                      has_lora ? (const __hip_bfloat16*)bw.data_ptr() : nullptr,
-                     (bias.defined() && bias.numel())
-                         ? (const __hip_bfloat16*)bias.data_ptr() : nullptr,
-                     (__hip_bfloat16*)y.data_ptr(), M, N, K, has_lora ? r : 0);
+                     bias_p,
+                     (__hip_bfloat16*)y.data_ptr(), M, N, K, r);
   HIP_CHECK_LAST();
   return y;
 }
@@ -928,20 +1003,19 @@ __global__ __launch_bounds__(512) void fused_nf4_gemm_kernel(
 torch::Tensor fused_nf4_gemm(torch::Tensor x, torch::Tensor qw, torch::Tensor amax,
                              long N, torch::Tensor t, torch::Tensor bw,
                              torch::Tensor bias, double lora_scale) {
-  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.is_contiguous());
-  TORCH_CHECK(qw.scalar_type() == torch::kUInt8 && amax.scalar_type() == torch::kFloat32);
+  const char* fn = "fused_nf4_gemm";
+  check_x(fn, x);
+  TORCH_CHECK(qw.scalar_type() == torch::kUInt8, fn, ": qw must be uint8");
   const long M = x.size(0), K = x.size(1);
-  TORCH_CHECK(qw.numel() == N * K / 2, "packed NF4 size mismatch");
   TORCH_CHECK(M % 256 == 0 && N % 256 == 0 && K % 64 == 0,
               "fused_nf4_gemm requires M%256==0, N%256==0, K%64==0");
-  int r = 0;
-  const bool has_lora = t.defined() && t.numel() > 0;
+  check_quant_w(fn, x, qw, amax, N, K, N * K / 2, 64);
+  const int r = check_lora(fn, x, t, bw, M, N, 64, 256);
+  const bool has_lora = r > 0;
+  const __hip_bfloat16* bias_p = check_bias(fn, x, bias, N);
   torch::Tensor t_scaled;
-  if (has_lora) {
-    r = (int)t.size(1);
-    TORCH_CHECK(r % 64 == 0 && r <= 256);
+  if (has_lora)
     t_scaled = (lora_scale == 1.0) ? t : (t * lora_scale).contiguous();
-  }
   auto y = torch::empty({M, N}, x.options());
   auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
   dim3 grid((M >> 8) * (N >> 8));
@@ -952,34 +1026,28 @@ torch::Tensor fused_nf4_gemm(torch::Tensor x, torch::Tensor qw, torch::Tensor am
                      amax.data_ptr<float>(),
                      has_lora ? (const __hip_bfloat16*)t_scaled.data_ptr() : nullptr,
                      has_lora ? (const __hip_bfloat16*)bw.data_ptr() : nullptr,
-                     (bias.defined() && bias.numel())
-                         ? (const __hip_bfloat16*)bias.data_ptr() : nullptr,
-                     (__hip_bfloat16*)y.data_ptr(), M, N, K, has_lora ? r : 0);
+                     bias_p,
+                     (__hip_bfloat16*)y.data_ptr(), M, N, K, r);
   HIP_CHECK_LAST();
   return y;
 }
 
 torch::Tensor fused_lora_gemm(torch::Tensor x, torch::Tensor w, torch::Tensor t,
                               torch::Tensor bw, torch::Tensor bias, double lora_scale) {
-  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.is_contiguous());
-  TORCH_CHECK(w.is_cuda() && w.dim() == 2 && w.is_contiguous());
-  TORCH_CHECK(x.scalar_type() == torch::kBFloat16 && w.scalar_type() == torch::kBFloat16);
+  const char* fn = "fused_lora_gemm";
+  check_x(fn, x);
+  check_dense_w(fn, x, w);
   const long M = x.size(0), K = x.size(1), N = w.size(0);
-  TORCH_CHECK(w.size(1) == K, "K mismatch");
   TORCH_CHECK(M % 256 == 0 && N % 256 == 0 && K % 64 == 0,
               "fused_lora_gemm requires M%256==0, N%256==0, K%64==0");
-  int r = 0;
-  const bool has_lora = t.defined() && t.numel() > 0;
+  const int r = check_lora(fn, x, t, bw, M, N, 64, 256);
+  const bool has_lora = r > 0;
+  const __hip_bfloat16* bias_p = check_bias(fn, x, bias, N);
   torch::Tensor t_scaled;
-  if (has_lora) {
-    TORCH_CHECK(bw.defined() && bw.is_contiguous() && t.is_contiguous());
-    r = (int)t.size(1);
-    TORCH_CHECK(t.size(0) == M && bw.size(0) == N && bw.size(1) == r);
-    TORCH_CHECK(r % 64 == 0 && r <= 256, "r must be a multiple of 64, <= 256");
-    // fold the LoRA scale into t (bf16 rounding of s*t matches the
-    // composed path, which also rounds t·B^T·s contributions in bf16)
+  // fold the LoRA scale into t (bf16 rounding of s*t matches the
+  // composed path, which also rounds t·B^T·s contributions in bf16)
+  if (has_lora)
     t_scaled = (lora_scale == 1.0) ? t : (t * lora_scale).contiguous();
-  }
   auto y = torch::empty({M, N}, x.options());
   auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
   const int nbn = (int)(N >> 8);
@@ -991,30 +1059,27 @@ torch::Tensor fused_lora_gemm(torch::Tensor x, torch::Tensor w, torch::Tensor t,
                      (const __hip_bfloat16*)w.data_ptr(),
                      has_lora ? (const __hip_bfloat16*)t_scaled.data_ptr() : nullptr,
                      has_lora ? (const __hip_bfloat16*)bw.data_ptr() : nullptr,
-                     (bias.defined() && bias.numel())
-                         ? (const __hip_bfloat16*)bias.data_ptr() : nullptr,
+                     bias_p,
                      (__hip_bfloat16*)y.data_ptr(), M, N, K,
-                     has_lora ? r : 0, (float)lora_scale);
+                     r, (float)lora_scale);
   HIP_CHECK_LAST();
   return y;
 }
 
 torch::Tensor fused_lora_gemm3(torch::Tensor x, torch::Tensor w, torch::Tensor t,
                                torch::Tensor bw, torch::Tensor bias, double lora_scale) {
-  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.is_contiguous());
-  TORCH_CHECK(w.is_cuda() && w.dim() == 2 && w.is_contiguous());
+  const char* fn = "fused_lora_gemm3";
+  check_x(fn, x);
+  check_dense_w(fn, x, w);
   const long M = x.size(0), K = x.size(1), N = w.size(0);
-  TORCH_CHECK(w.size(1) == K);
   TORCH_CHECK(M % 256 == 0 && N % 128 == 0 && K % 64 == 0,
               "fused_lora_gemm3 requires M%256==0, N%128==0, K%64==0");
-  int r = 0;
-  const bool has_lora = t.defined() && t.numel() > 0;
+  const int r = check_lora(fn, x, t, bw, M, N, 64, 128);
+  const bool has_lora = r > 0;
+  const __hip_bfloat16* bias_p = check_bias(fn, x, bias, N);
   torch::Tensor t_scaled;
-  if (has_lora) {
-    r = (int)t.size(1);
-    TORCH_CHECK(r % 64 == 0 && r <= 128);
+  if (has_lora)
     t_scaled = (lora_scale == 1.0) ? t : (t * lora_scale).contiguous();
-  }
   auto y = torch::empty({M, N}, x.options());
   auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
   dim3 grid((M >> 8) * (N >> 7));
@@ -1025,30 +1090,27 @@ torch::Tensor fused_lora_gemm3(torch::Tensor x, torch::Tensor w, torch::Tensor t
                      (const __hip_bfloat16*)w.data_ptr(),
                      has_lora ? (const __hip_bfloat16*)t_scaled.data_ptr() : nullptr,
                      has_lora ? (const __hip_bfloat16*)bw.data_ptr() : nullptr,
-                     (bias.defined() && bias.numel())
-                         ? (const __hip_bfloat16*)bias.data_ptr() : nullptr,
+                     bias_p,
                      (__hip_bfloat16*)y.data_ptr(), M, N, K,
-                     has_lora ? r : 0, (float)lora_scale);
+                     r, (float)lora_scale);
   HIP_CHECK_LAST();
   return y;
 }
 
 torch::Tensor fused_lora_gemm4(torch::Tensor x, torch::Tensor w, torch::Tensor t,
                                torch::Tensor bw, torch::Tensor bias, double lora_scale) {
-  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.is_contiguous());
-  TORCH_CHECK(w.is_cuda() && w.dim() == 2 && w.is_contiguous());
+  const char* fn = "fused_lora_gemm4";
+  check_x(fn, x);
+  check_dense_w(fn, x, w);
   const long M = x.size(0), K = x.size(1), N = w.size(0);
-  TORCH_CHECK(w.size(1) == K);
   TORCH_CHECK(M % 256 == 0 && N % 256 == 0 && K % 32 == 0,
               "fused_lora_gemm4 requires M%256==0, N%256==0, K%32==0");
-  int r = 0;
-  const bool has_lora = t.defined() && t.numel() > 0;
+  const int r = check_lora(fn, x, t, bw, M, N, 32, 256);
+  const bool has_lora = r > 0;
+  const __hip_bfloat16* bias_p = check_bias(fn, x, bias, N);
   torch::Tensor t_scaled;
-  if (has_lora) {
-    r = (int)t.size(1);
-    TORCH_CHECK(r % 32 == 0 && r <= 256);
+  if (has_lora)
     t_scaled = (lora_scale == 1.0) ? t : (t * lora_scale).contiguous();
-  }
   auto y = torch::empty({M, N}, x.options());
   auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
   dim3 grid((M >> 8) * (N >> 8));
@@ -1059,9 +1121,8 @@ torch::Tensor fused_lora_gemm4(torch::Tensor x, torch::Tensor w, torch::Tensor t
                      (const __hip_bfloat16*)w.data_ptr(),
                      has_lora ? (const __hip_bfloat16*)t_scaled.data_ptr() : nullptr,
                      has_lora ? (const __hip_bfloat16*)bw.data_ptr() : nullptr,
-                     (bias.defined() && bias.numel())
-                         ? (const __hip_bfloat16*)bias.data_ptr() : nullptr,
-                     (__hip_bfloat16*)y.data_ptr(), M, N, K, has_lora ? r : 0);
+                     bias_p,
+                     (__hip_bfloat16*)y.data_ptr(), M, N, K, r);
   HIP_CHECK_LAST();
   return y;
 }
