@@ -144,6 +144,9 @@ def check_args_torchrun_main(args, n_cli_args=None):
             "Pythia attends across document boundaries"
         )
 
+    if getattr(args, "qk_norm", None) is not None and _is_pythia_run(args):
+        raise ValueError("--qk_norm is implemented for the LLaMA models only")
+
     if args.distributed_type == "fsdp":
         raise NotImplementedError(
             "FSDP is not supported (it is hard-disabled in the reference too); use ddp"

@@ -34,6 +34,7 @@ class LlamaConfig(PretrainedConfig):
         eos_token_id=1,
         tie_word_embeddings=False,
         rope_theta=10000.0,
+        qk_norm=False,
         **kwargs,
     ):
         self.vocab_size = vocab_size
@@ -59,6 +60,9 @@ class LlamaConfig(PretrainedConfig):
         self.rms_norm_eps = rms_norm_eps
         self.use_cache = use_cache
         self.rope_theta = rope_theta
+        # RMSNorm over head_dim of every q and k head before the rotary
+        # embedding (Qwen3's q_norm / k_norm); off: the plain LLaMA attention
+        self.qk_norm = bool(qk_norm)
         super().__init__(
             pad_token_id=pad_token_id,
             bos_token_id=bos_token_id,
@@ -74,6 +78,9 @@ class LlamaConfig(PretrainedConfig):
         d = super().to_dict()
         if d.get("num_key_value_heads") == d.get("num_attention_heads"):
             d.pop("num_key_value_heads", None)
+        # likewise `qk_norm`: only a config that turns it on carries the field
+        if not d.get("qk_norm"):
+            d.pop("qk_norm", None)
         return d
 
 

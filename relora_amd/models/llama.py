@@ -115,6 +115,13 @@ class LlamaAttention(nn.Module):
             self.head_dim, max_position_embeddings=config.max_position_embeddings,
             base=getattr(config, "rope_theta", 10000.0),
         )
+        # per-head RMSNorm of q and k before the rotary embedding, one weight
+        # [head_dim] per tensor shared by its heads (Qwen3's module names, so
+        # its checkpoints load key for key)
+        self.qk_norm = bool(getattr(config, "qk_norm", False))
+        if self.qk_norm:
+            self.q_norm = LlamaRMSNorm(self.head_dim, eps=config.rms_norm_eps)
+            self.k_norm = LlamaRMSNorm(self.head_dim, eps=config.rms_norm_eps)
 
     def forward(
         self,
@@ -133,9 +140,11 @@ class LlamaAttention(nn.Module):
         cos, sin = self.rotary_emb(hidden_states, seq_len=kv_seq_len)
         # positions 0..q_len-1 (training, prefill without a cache): q and k come
         # out of the projection group already rotated — on the group's HIP path
-        # by its LoRA epilogue kernel, elsewhere by ops.rope, the same values
+        # by its LoRA epilogue kernel, elsewhere by ops.rope, the same values.
+        # With config.qk_norm the projections come out unrotated, and one
+        # ops.qk_norm_rope call norms and rotates q and k
         rope_in_group = (position_ids is None and past_key_value is None
-                         and cos.shape[0] >= q_len)
+                         and cos.shape[0] >= q_len and not self.qk_norm)
         proj = (self.q_proj, self.k_proj, self.v_proj)
         if rope_in_group:
             q, k, v = lora_group_forward(
@@ -151,7 +160,12 @@ class LlamaAttention(nn.Module):
                 position_ids = torch.arange(
                     kv_seq_len - q_len, kv_seq_len, device=hidden_states.device
                 ).unsqueeze(0)
-            q, k = ops.rope(q, k, cos, sin, position_ids=position_ids)
+            if self.qk_norm:
+                q, k = ops.qk_norm_rope(
+                    q, k, self.q_norm.weight, self.k_norm.weight, cos, sin,
+                    self.q_norm.variance_epsilon, position_ids=position_ids)
+            else:
+                q, k = ops.rope(q, k, cos, sin, position_ids=position_ids)
 
         if past_key_value is not None:
             k = torch.cat([past_key_value[0], k], dim=2)

@@ -20,6 +20,17 @@ std::vector<torch::Tensor> layernorm_bwd(torch::Tensor x, torch::Tensor w,
 std::vector<torch::Tensor> rope_fwd(torch::Tensor q, torch::Tensor k,
                                     torch::Tensor cos_t, torch::Tensor sin_t,
                                     bool inverse, bool force_scalar);
+// qk_norm_rope.hip
+std::vector<torch::Tensor> qk_norm_rope_fwd(torch::Tensor q, torch::Tensor k,
+                                            torch::Tensor wq, torch::Tensor wk,
+                                            torch::Tensor cos_t, torch::Tensor sin_t,
+                                            double eps);
+std::vector<torch::Tensor> qk_norm_rope_bwd(torch::Tensor dqo, torch::Tensor dko,
+                                            torch::Tensor q, torch::Tensor k,
+                                            torch::Tensor wq, torch::Tensor wk,
+                                            torch::Tensor invrms_q, torch::Tensor invrms_k,
+                                            torch::Tensor cos_t, torch::Tensor sin_t);
+std::vector<int64_t> qk_norm_rope_geometry(int64_t hd);
 // swiglu.hip
 torch::Tensor swiglu_fwd(torch::Tensor g, torch::Tensor u);
 torch::Tensor gelu_fwd(torch::Tensor x);
@@ -118,6 +129,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rope_fwd", &rope_fwd, "RoPE apply fwd/inverse (gfx950)",
         py::arg("q"), py::arg("k"), py::arg("cos"), py::arg("sin"), py::arg("inverse"),
         py::arg("force_scalar") = false);
+  m.def("qk_norm_rope_fwd", &qk_norm_rope_fwd,
+        "per-head RMSNorm of q and k fused with RoPE, one launch (gfx950)",
+        py::arg("q"), py::arg("k"), py::arg("wq"), py::arg("wk"), py::arg("cos"),
+        py::arg("sin"), py::arg("eps"));
+  m.def("qk_norm_rope_bwd", &qk_norm_rope_bwd,
+        "backward of qk_norm_rope_fwd: dq, dk and the fp32 weight gradients (gfx950)",
+        py::arg("dqo"), py::arg("dko"), py::arg("q"), py::arg("k"), py::arg("wq"),
+        py::arg("wk"), py::arg("invrms_q"), py::arg("invrms_k"), py::arg("cos"),
+        py::arg("sin"));
+  m.def("qk_norm_rope_geometry", &qk_norm_rope_geometry,
+        "(rows per block, backward block cap per tensor) of qk_norm_rope for a head_dim");
   m.def("swiglu_fwd", &swiglu_fwd, "SwiGLU forward (gfx950)");
   m.def("swiglu_bwd", &swiglu_bwd, "SwiGLU backward (gfx950)");
   m.def("gelu_fwd", &gelu_fwd, "exact-erf GELU forward (gfx950)");

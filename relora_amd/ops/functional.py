@@ -222,6 +222,75 @@ def rope(q, k, cos, sin, position_ids=None):
 
 
 # ---------------------------------------------------------------------------
+# Per-head QK RMSNorm + RoPE (Qwen3 convention): RMSNorm over head_dim of
+# every head of q and k, one [head_dim] weight per tensor, then the rotary
+# embedding.  One HIP kernel in each direction (ops/csrc/qk_norm_rope.hip).
+# ---------------------------------------------------------------------------
+
+
+def qk_norm_rope_torch(q, k, wq, wk, cos, sin, eps, position_ids=None):
+    """rmsnorm_torch over the last dim of q and k, then rope_torch."""
+    return rope_torch(rmsnorm_torch(q, wq, eps), rmsnorm_torch(k, wk, eps),
+                      cos, sin, position_ids)
+
+
+class _HipQKNormRope(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, wq, wk, cos, sin, eps):
+        if not _attn_layout_ok(q):
+            q = q.contiguous()
+        if not _attn_layout_ok(k):
+            k = k.contiguous()
+        # kernel contract, as for _HipRoPE: fp32 contiguous tables
+        cos = cos.float().contiguous()
+        sin = sin.float().contiguous()
+        wq, wk = wq.contiguous(), wk.contiguous()
+        qo, ko, iq, ik = hip.ext().qk_norm_rope_fwd(q, k, wq, wk, cos, sin, eps)
+        ctx.save_for_backward(q, k, wq, wk, iq, ik, cos, sin)
+        return qo, ko
+
+    @staticmethod
+    def backward(ctx, dqo, dko):
+        q, k, wq, wk, iq, ik, cos, sin = ctx.saved_tensors
+        # the kernel walks dy with x's strides
+        if not _same_layout(dqo, q):
+            dqo = torch.empty_like(q).copy_(dqo)
+        if not _same_layout(dko, k):
+            dko = torch.empty_like(k).copy_(dko)
+        dq, dk, dwq, dwk = hip.ext().qk_norm_rope_bwd(dqo, dko, q, k, wq, wk, iq, ik, cos, sin)
+        return dq, dk, dwq.to(wq.dtype), dwk.to(wk.dtype), None, None, None
+
+
+def _qk_norm_rope_hip_ok(q, k, wq, wk, cos, sin):
+    """What qk_norm_rope_fwd takes: bf16 q, k and weights, head_dim a multiple
+    of 16 and <= 128, full rotary, tables that cover the sequence.  head_dim
+    52 (llama_40m), fp32 and partial rotary are the torch composition's."""
+    hd = q.shape[-1]
+    return (q.dim() == 4 and k.dim() == 4
+            and q.dtype == torch.bfloat16 and k.dtype == torch.bfloat16
+            and wq.dtype == torch.bfloat16 and wk.dtype == torch.bfloat16
+            and k.device == q.device
+            and k.shape[0] == q.shape[0] and k.shape[2:] == q.shape[2:]
+            and hd % 16 == 0 and hd <= 128
+            and wq.shape == (hd,) and wk.shape == (hd,)
+            and cos.dim() == 2 and cos.shape == sin.shape
+            and cos.shape[1] == hd and cos.shape[0] >= q.shape[2]
+            and all(t.data_ptr() % 16 == 0 and t.storage_offset() % 8 == 0
+                    for t in (q, k, wq, wk)))
+
+
+def qk_norm_rope(q, k, wq, wk, cos, sin, eps=1e-6, position_ids=None):
+    """Per-head RMSNorm of q [B, nh, S, hd] and k [B, nkv, S, hd] with the
+    weights wq, wk [hd], then the rotary embedding: the q/k treatment of
+    Qwen3-style attention.  position_ids (the kv-cache path) is supported on
+    the torch path only, like `rope`."""
+    if (position_ids is None and hip.use_hip(q, "qk_norm")
+            and _qk_norm_rope_hip_ok(q, k, wq, wk, cos, sin)):
+        return _HipQKNormRope.apply(q, k, wq, wk, cos, sin, float(eps))
+    return qk_norm_rope_torch(q, k, wq, wk, cos, sin, eps, position_ids)
+
+
+# ---------------------------------------------------------------------------
 # SwiGLU (K7)
 # ---------------------------------------------------------------------------
 

@@ -94,6 +94,12 @@ def parse_args(args=None):
                         help="Token that ends a document for --intra_doc_masking. Default: the "
                              "tokenizer's eos_token_id, else the model config's.")
 
+    parser.add_argument("--qk_norm", default=None,
+                        type=lambda x: None if x is None else x.lower() == "true",
+                        help="RMSNorm over every q and k head before RoPE (LLaMA only; Qwen3's "
+                             "q_norm / k_norm). Sets the field of a config given by "
+                             "--model_config; a loaded checkpoint's own config decides.")
+
     parser.add_argument("--batch_size", type=_int_or_auto, default=None,
                         help="micro-batch per GPU, or 'auto' to size for the device HBM (288 GB on MI355X)")
     parser.add_argument("--gradient_accumulation", type=int, default=None)
@@ -164,6 +170,39 @@ def parse_args(args=None):
     args = parser.parse_args(args)
     args = args_utils.check_args_torchrun_main(args, n_cli_args=n_cli)
     return args
+
+
+def resolve_qk_norm(args, model_config, from_checkpoint):
+    """Apply --qk_norm to `model_config` (in place) and return the config's
+    setting.  The flag sets the field of a freshly built LLaMA config; a
+    config that came with a checkpoint decides for itself, and a flag that
+    contradicts it is an error (the checkpoint has, or lacks, the q_norm /
+    k_norm weights)."""
+    flag = getattr(args, "qk_norm", None)
+    if flag is None:
+        return bool(getattr(model_config, "qk_norm", False))
+    flag = bool(flag)
+    if getattr(model_config, "model_type", "llama") != "llama":
+        raise ValueError("--qk_norm is implemented for the LLaMA models only")
+    if from_checkpoint:
+        if bool(model_config.qk_norm) != flag:
+            raise ValueError(
+                f"--qk_norm {str(flag).lower()} conflicts with the loaded checkpoint's config "
+                f"(qk_norm={bool(model_config.qk_norm)}); drop the flag, the checkpoint's "
+                f"config decides")
+    else:
+        model_config.qk_norm = flag
+    return flag
+
+
+def _checkpoint_qk_norm(path):
+    """qk_norm of the config.json next to a checkpoint's weights, or None when
+    the directory has none."""
+    cfg_file = os.path.join(path, "config.json")
+    if not os.path.exists(cfg_file):
+        return None
+    with open(cfg_file) as f:
+        return bool(json.load(f).get("qk_norm", False))
 
 
 def resolve_doc_separator_id(args, tokenizer, model_config):
@@ -347,6 +386,7 @@ def main(args):
         if args.model_config is None:
             raise ValueError("--batch_size auto requires --model_config")
         _cfg = load_model_config(args.model_config)
+        resolve_qk_norm(args, _cfg, from_checkpoint=False)
         args.batch_size = auto_micro_batch(
             _cfg, args.max_length, args.total_batch_size, world_size,
             lora_r=(args.lora_r or 0) if args.use_peft else 0,
@@ -473,10 +513,20 @@ def main(args):
                 )
                 if not (model_config.vocab_size == 32000 and t_vocab == 32100):
                     raise ValueError("Model config vocab size does not match tokenizer vocab size")
+        resolve_qk_norm(args, model_config, from_checkpoint=False)
+        # weights loaded into the fresh model must have been saved with the
+        # same setting
+        for ckpt in (args.warmed_up_model, args.resume_from):
+            saved = _checkpoint_qk_norm(ckpt) if ckpt else None
+            if saved is not None and saved != bool(getattr(model_config, "qk_norm", False)):
+                raise ValueError(
+                    f"qk_norm={bool(getattr(model_config, 'qk_norm', False))} conflicts with "
+                    f"the config of the checkpoint {ckpt} (qk_norm={saved})")
         model = build_model_from_config(model_config)
     else:
         logger.info(f"Loading local model from {args.model_name_or_path}")
         model_config = load_model_config(args.model_name_or_path)
+        resolve_qk_norm(args, model_config, from_checkpoint=True)
         model = build_model_from_config(model_config)
         state_path = os.path.join(args.model_name_or_path, "pytorch_model.bin")
         if os.path.exists(state_path):

@@ -35,6 +35,8 @@ def estimate_param_count(cfg, lora_r=0):
     KV = _kv_width(cfg)
     # per layer: q and o are H x H, k and v are H x KV
     n_params = V * H * 2 + L * (2 * H * H + 2 * H * KV + 3 * H * I + 2 * H) + H
+    if getattr(cfg, "qk_norm", False):
+        n_params += L * 2 * (H // cfg.num_attention_heads)  # q_norm, k_norm
     lora_params = (L * lora_r * (2 * (H + H) + 2 * (H + KV) + 2 * (H + I) + (I + H))
                    if lora_r else 0)
     return n_params, lora_params
@@ -65,6 +67,12 @@ def estimate_step_bytes(cfg, micro_batch, seq_len, dtype=torch.bfloat16,
     act_layer = T * (5 * H + 2 * KV + 4 * I) * e
     # attention saves q,o (H each), k,v (KV each) + lse
     act_attn = T * (2 * H + 2 * KV) * e + T * nh * 4
+    if getattr(cfg, "qk_norm", False):
+        # qk_norm_rope saves its inputs, the pre-norm q and k (attention's
+        # saved q and k are the normed, rotated ones), and one fp32 invrms
+        # per q and k head row
+        nkv = getattr(cfg, "num_key_value_heads", None) or nh
+        act_attn += T * (H + KV) * e + T * (nh + nkv) * 4
     acts = L * (act_layer + act_attn)
     # logits path: bf16 logits + grad (chunked CE still peaks at one chunk)
     ce = 2 * min(T, 16384) * V * e

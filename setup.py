@@ -32,6 +32,7 @@ ext = CUDAExtension(
         os.path.join(CSRC, "bindings.cpp"),
         os.path.join(CSRC, "norms.hip"),
         os.path.join(CSRC, "rope.hip"),
+        os.path.join(CSRC, "qk_norm_rope.hip"),
         os.path.join(CSRC, "swiglu.hip"),
         os.path.join(CSRC, "ce.hip"),
         os.path.join(CSRC, "adamw.hip"),
