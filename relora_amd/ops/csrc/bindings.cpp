@@ -110,6 +110,13 @@ std::vector<torch::Tensor> quantize_nf4(torch::Tensor x);
 torch::Tensor dequantize_nf4(torch::Tensor q, torch::Tensor absmax, long n, torch::ScalarType dtype);
 std::vector<torch::Tensor> quantize_int8(torch::Tensor x);
 torch::Tensor dequantize_int8(torch::Tensor q, torch::Tensor absmax, long n, torch::ScalarType dtype);
+// fp8_gemm.hip
+std::vector<torch::Tensor> quantize_rows_fp8(torch::Tensor x);
+torch::Tensor dequantize_rows_fp8(torch::Tensor q, torch::Tensor absmax, long R, long K,
+                                  torch::ScalarType dtype);
+torch::Tensor fused_fp8_gemm(torch::Tensor xq, torch::Tensor xs, torch::Tensor wq,
+                             torch::Tensor ws, long N, torch::Tensor t, torch::Tensor bw,
+                             torch::Tensor bias, double lora_scale);
 // attention.hip
 std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor v,
                                     double scale, c10::optional<torch::Tensor> doc_start);
@@ -203,6 +210,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dequantize_nf4", &dequantize_nf4, "NF4 blockwise dequantize (gfx950)");
   m.def("quantize_int8", &quantize_int8, "int8 blockwise quantize (gfx950)");
   m.def("dequantize_int8", &dequantize_int8, "int8 blockwise dequantize (gfx950)");
+  m.def("quantize_rows_fp8", &quantize_rows_fp8,
+        "bf16 [R,K] -> (e4m3 codes uint8 [R,K], fp32 absmax [R]), one scale per row (gfx950)");
+  m.def("dequantize_rows_fp8", &dequantize_rows_fp8,
+        "e4m3 codes + per-row absmax -> bf16/fp32 [R,K] (gfx950)");
+  // xs / ws: the per-row absmax of quantize_rows_fp8 (scale = absmax/448)
+  m.def("fused_fp8_gemm", &fused_fp8_gemm,
+        "y = (xq@wq^T)*sx*sw^T (+bias) + s*t@Bw^T on the f8f6f4 MFMA, 256^2 glds tile (gfx950)",
+        py::arg("xq"), py::arg("xs"), py::arg("wq"), py::arg("ws"), py::arg("N"),
+        py::arg("t"), py::arg("bw"), py::arg("bias"), py::arg("lora_scale"));
   // doc_start: optional int32 [B, S] intra-document mask (padded head_dim <= 64)
   m.def("attn_fwd", &attn_fwd, "causal flash attention forward (gfx950 MFMA)",
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("scale"),

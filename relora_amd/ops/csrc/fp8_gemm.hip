@@ -1,0 +1,538 @@
+// Some packed-fp32 instruction forms miscompute on this target, so this file
+// is compiled without them.  The attribute has to cover the headers too: a
+// helper that lacks it is not inlined into a function that has it.
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma clang attribute push(__attribute__((target("no-packed-fp32-ops"))), apply_to = function)
+#endif
+#include "hip/hip_runtime.h"
+// FP8 frozen-W path (`--quantize fp8`) on the gfx950 f8f6f4 matrix cores.
+//
+// Format: OCP e4m3 (e4m3fn, max 448), ONE fp32 absmax per row, no block
+// scales.  For a row v:  inv = 448/absmax (one IEEE fp32 division),
+// code = e4m3_rne(v*inv) with the product rounded to fp32,
+// value = float(code) * (absmax/448).  A row of zeros encodes to zeros.
+// W [N,K] is quantised per output row (once per merge cycle), activations
+// [M,K] per token row at every forward.  Both scales are rank-1 over the
+// output, so the MFMA loop runs on raw codes and the scales enter in the
+// epilogue only:  y[m,n] = acc[m,n] * (ax[m]/448) * (aw[n]/448).
+//
+//   quantize_rows_fp8    bf16 [R,K] -> (uint8 codes [R,K], fp32 absmax [R])
+//   dequantize_rows_fp8  codes, absmax -> bf16 | fp32 [R,K]
+//   fused_fp8_gemm       y = (xq·wq^T)·sx·sw^T (+bias) + s·t·Bw^T, bf16 out
+//
+// GEMM structure: the 256x256 / 8-wave / double-buffered-glds geometry of
+// fused_lora_gemm, redesigned for one-byte operands.  An LDS row stays
+// 128 bytes — now 128 k — so a K-tile carries twice the k of the bf16 kernel
+// for the same bytes, the same glds count and the same barrier count, and one
+// v_mfma_f32_16x16x128_f8f6f4 per C fragment consumes the whole tile row.
+//
+// Tile instruction: 16x16x128 rather than 32x32x64.  Per 128 k a wave's
+// 128x64 tile needs 12 32-byte fragments either way, so LDS traffic is the
+// same; 16x16x128 keeps the 16x16 C layout (col = lane&15, row =
+// (lane>>4)*4+reg), so the rank-r LoRA update lands on the SAME accumulators
+// with the 16x16x32 bf16 MFMAs and the LDS-staged b128 store epilogue of
+// fused_lora_gemm carries over unchanged.
+//
+// Lane-to-k assignment: a dot product is invariant under any permutation of
+// k that A and B share, so lane (row fr = lane&15, group fq = lane>>4) takes
+// its 32 bytes as the two 16-byte chunks {fq, 4+fq} of the row (k =
+// fq*16..+16 and 64+fq*16..+16) rather than 32 consecutive k.  With the
+// swizzle  chunk ^= (row>>1)&7  every 16-lane ds_read_b128 service group
+// covers all 16 16-byte bank slots exactly once: conflict-free for both
+// reads of the fp8 fragments and for the bf16 LoRA fragments (chunk
+// ks*4+fq), checked with tools/lds_bank_model.py (fp8_gemm_* patterns).
+
+#include <ATen/hip/HIPContext.h>
+#include <torch/extension.h>
+
+#include "common.h"
+
+typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_q;
+typedef __attribute__((ext_vector_type(4))) float f32x4_q;
+typedef __attribute__((ext_vector_type(4))) int i32x4_q;
+typedef __attribute__((ext_vector_type(8))) int i32x8_q;
+
+#define FP8_MAX 448.0f
+
+// ---------------------------------------------------------------------------
+// Row quantiser.  One pass over HBM: a row sits on G lanes (a wave, or 16
+// lanes for K <= 256), each lane keeps NU units of 16 bf16 (two bf16x8 loads)
+// in registers between the shuffle max-reduction and the packed conversion,
+// and stores 16 codes per unit with one 16-byte store.  NU == 0 is the
+// looping form for K > 8192 (second read of the row comes from L2).
+// ---------------------------------------------------------------------------
+
+struct Unit16 { uint4 lo, hi; };  // 16 bf16
+
+DEV_INLINE float unit_absmax(const Unit16& u) {
+  const unsigned w[8] = {u.lo.x, u.lo.y, u.lo.z, u.lo.w, u.hi.x, u.hi.y, u.hi.z, u.hi.w};
+  float am = 0.f;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    am = fmaxf(am, fabsf(__uint_as_float(w[i] << 16)));
+    am = fmaxf(am, fabsf(__uint_as_float(w[i] & 0xffff0000u)));
+  }
+  return am;
+}
+
+DEV_INLINE uint4 unit_encode(const Unit16& u, float inv) {
+  const unsigned w[8] = {u.lo.x, u.lo.y, u.lo.z, u.lo.w, u.hi.x, u.hi.y, u.hi.z, u.hi.w};
+  unsigned o[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const float a = __fmul_rn(__uint_as_float(w[2 * i] << 16), inv);
+    const float b = __fmul_rn(__uint_as_float(w[2 * i] & 0xffff0000u), inv);
+    const float c = __fmul_rn(__uint_as_float(w[2 * i + 1] << 16), inv);
+    const float d = __fmul_rn(__uint_as_float(w[2 * i + 1] & 0xffff0000u), inv);
+    int p = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
+    p = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, p, true);
+    o[i] = (unsigned)p;
+  }
+  return make_uint4(o[0], o[1], o[2], o[3]);
+}
+
+template <int G>
+DEV_INLINE float group_max(float am) {
+#pragma unroll
+  for (int off = G / 2; off > 0; off >>= 1) am = fmaxf(am, __shfl_xor(am, off));
+  return am;
+}
+
+template <int G, int NU>
+__global__ __launch_bounds__(256) void quantize_rows_fp8_kernel(
+    const __hip_bfloat16* __restrict__ x, uint8_t* __restrict__ q,
+    float* __restrict__ absmax, long R, int K) {
+  const int gl = threadIdx.x & (G - 1);
+  const long row = ((long)blockIdx.x * 256 + threadIdx.x) / G;
+  const bool live = row < R;  // whole lane groups: shuffles stay inside a row
+  const int units = K >> 4;
+  const Unit16* src = reinterpret_cast<const Unit16*>(x + (live ? row : 0) * K);
+  uint4* dst = reinterpret_cast<uint4*>(q + (live ? row : 0) * K);
+  float am = 0.f;
+  if (NU > 0) {
+    Unit16 u[NU > 0 ? NU : 1];
+#pragma unroll
+    for (int i = 0; i < NU; ++i) {
+      const int c = gl + i * G;
+      u[i] = (live && c < units) ? src[c] : Unit16{make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0)};
+      am = fmaxf(am, unit_absmax(u[i]));
+    }
+    am = group_max<G>(am);
+    const float inv = am > 0.f ? __fdiv_rn(FP8_MAX, am) : 0.f;
+#pragma unroll
+    for (int i = 0; i < NU; ++i) {
+      const int c = gl + i * G;
+      if (live && c < units) dst[c] = unit_encode(u[i], inv);
+    }
+  } else {
+    if (live)
+      for (int c = gl; c < units; c += G) am = fmaxf(am, unit_absmax(src[c]));
+    am = group_max<G>(am);
+    const float inv = am > 0.f ? __fdiv_rn(FP8_MAX, am) : 0.f;
+    if (live)
+      for (int c = gl; c < units; c += G) dst[c] = unit_encode(src[c], inv);
+  }
+  if (live && gl == 0) absmax[row] = am;
+}
+
+// any K (weights whose in_features is no multiple of 16, e.g. 5461): one wave
+// per row, scalar loads, byte stores.  Off the hot path (once per merge).
+__global__ __launch_bounds__(256) void quantize_rows_fp8_any_kernel(
+    const __hip_bfloat16* __restrict__ x, uint8_t* __restrict__ q,
+    float* __restrict__ absmax, long R, int K) {
+  const int lane = threadIdx.x & 63;
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const bool live = row < R;
+  const __hip_bfloat16* src = x + (live ? row : 0) * K;
+  float am = 0.f;
+  if (live)
+    for (int k = lane; k < K; k += 64) am = fmaxf(am, fabsf(to_f32(src[k])));
+  am = group_max<64>(am);
+  if (!live) return;
+  const float inv = am > 0.f ? __fdiv_rn(FP8_MAX, am) : 0.f;
+  for (int k = lane; k < K; k += 64) {
+    const int p = __builtin_amdgcn_cvt_pk_fp8_f32(__fmul_rn(to_f32(src[k]), inv), 0.f, 0, false);
+    q[row * K + k] = (uint8_t)(p & 0xff);
+  }
+  if (lane == 0) absmax[row] = am;
+}
+
+template <int G, int NU>
+static void launch_quantize(const torch::Tensor& x, torch::Tensor& q, torch::Tensor& am,
+                            long R, int K, hipStream_t stream) {
+  const long rows_per_block = 256 / G;
+  dim3 grid((unsigned)((R + rows_per_block - 1) / rows_per_block)), block(256);
+  hipLaunchKernelGGL((quantize_rows_fp8_kernel<G, NU>), grid, block, 0, stream,
+                     (const __hip_bfloat16*)x.data_ptr(), q.data_ptr<uint8_t>(),
+                     am.data_ptr<float>(), R, K);
+}
+
+std::vector<torch::Tensor> quantize_rows_fp8(torch::Tensor x) {
+  const char* fn = "quantize_rows_fp8";
+  TORCH_CHECK(x.is_cuda(), fn, ": x must be a GPU tensor");
+  TORCH_CHECK(x.dim() == 2, fn, ": x must be 2-D [R, K]");
+  TORCH_CHECK(x.is_contiguous(), fn, ": x must be contiguous");
+  TORCH_CHECK(x.scalar_type() == torch::kBFloat16, fn, ": x must be bf16");
+  const long R = x.size(0), K = x.size(1);
+  TORCH_CHECK(R > 0 && K > 0, fn, ": R and K must be > 0");
+  TORCH_CHECK(K < (1L << 31) && R < (1L << 31) * 4, fn, ": shape too large");
+  auto q = torch::empty({R, K}, x.options().dtype(torch::kUInt8));
+  auto am = torch::empty({R}, x.options().dtype(torch::kFloat32));
+  auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
+  const int k = (int)K;
+  if (K % 16 != 0) {
+    hipLaunchKernelGGL(quantize_rows_fp8_any_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256),
+                       0, stream, (const __hip_bfloat16*)x.data_ptr(), q.data_ptr<uint8_t>(),
+                       am.data_ptr<float>(), R, k);
+  } else if (K <= 256) {
+    launch_quantize<16, 1>(x, q, am, R, k, stream);
+  } else if (K <= 1024) {
+    launch_quantize<64, 1>(x, q, am, R, k, stream);
+  } else if (K <= 2048) {
+    launch_quantize<64, 2>(x, q, am, R, k, stream);
+  } else if (K <= 4096) {
+    launch_quantize<64, 4>(x, q, am, R, k, stream);
+  } else if (K <= 8192) {
+    launch_quantize<64, 8>(x, q, am, R, k, stream);
+  } else {
+    launch_quantize<64, 0>(x, q, am, R, k, stream);
+  }
+  HIP_CHECK_LAST();
+  return {q, am};
+}
+
+// ---------------------------------------------------------------------------
+// Row dequantiser: value = float(code) * (absmax/448), rounded once to T.
+// VEC: one thread per 16 codes (K % 16 == 0); otherwise one per code.
+// ---------------------------------------------------------------------------
+
+template <typename T, bool VEC>
+__global__ __launch_bounds__(256) void dequantize_rows_fp8_kernel(
+    const uint8_t* __restrict__ q, const float* __restrict__ absmax,
+    T* __restrict__ out, long n, int K) {
+  const long i = ((long)blockIdx.x * 256 + threadIdx.x) * (VEC ? 16 : 1);
+  if (i >= n) return;
+  const float sc = __fdiv_rn(absmax[i / K], FP8_MAX);
+  if (VEC) {
+    const uint4 c = *reinterpret_cast<const uint4*>(q + i);
+    const unsigned w[4] = {c.x, c.y, c.z, c.w};
+    T v[16];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      v[4 * j + 0] = from_f32<T>(__fmul_rn(__builtin_amdgcn_cvt_f32_fp8(w[j], 0), sc));
+      v[4 * j + 1] = from_f32<T>(__fmul_rn(__builtin_amdgcn_cvt_f32_fp8(w[j], 1), sc));
+      v[4 * j + 2] = from_f32<T>(__fmul_rn(__builtin_amdgcn_cvt_f32_fp8(w[j], 2), sc));
+      v[4 * j + 3] = from_f32<T>(__fmul_rn(__builtin_amdgcn_cvt_f32_fp8(w[j], 3), sc));
+    }
+    store8(out + i, *reinterpret_cast<const Vec8<T>*>(v));
+    store8(out + i + 8, *reinterpret_cast<const Vec8<T>*>(v + 8));
+  } else {
+    out[i] = from_f32<T>(__fmul_rn(__builtin_amdgcn_cvt_f32_fp8((unsigned)q[i], 0), sc));
+  }
+}
+
+torch::Tensor dequantize_rows_fp8(torch::Tensor q, torch::Tensor absmax, long R, long K,
+                                  torch::ScalarType dtype) {
+  const char* fn = "dequantize_rows_fp8";
+  TORCH_CHECK(q.is_cuda(), fn, ": codes must be a GPU tensor");
+  TORCH_CHECK(q.scalar_type() == torch::kUInt8 && q.is_contiguous(), fn,
+              ": codes must be contiguous uint8");
+  TORCH_CHECK(R > 0 && K > 0 && K < (1L << 31), fn, ": bad R or K");
+  TORCH_CHECK(q.numel() == R * K, fn, ": codes must hold R*K values");
+  TORCH_CHECK(absmax.device() == q.device() && absmax.scalar_type() == torch::kFloat32 &&
+                  absmax.is_contiguous() && absmax.numel() == R,
+              fn, ": absmax must be R contiguous fp32 values on the codes' device");
+  TORCH_CHECK(dtype == torch::kBFloat16 || dtype == torch::kFloat32, fn,
+              ": output dtype must be bf16 or fp32");
+  auto out = torch::empty({R, K}, q.options().dtype(dtype));
+  auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
+  const long n = R * K;
+  const bool vec = K % 16 == 0;
+  const long threads = vec ? n / 16 : n;
+  dim3 grid((unsigned)((threads + 255) / 256)), block(256);
+  const uint8_t* qp = q.data_ptr<uint8_t>();
+  const float* ap = absmax.data_ptr<float>();
+#define LAUNCH_DQ(T, PTR, V)                                                          \
+  hipLaunchKernelGGL((dequantize_rows_fp8_kernel<T, V>), grid, block, 0, stream, qp,  \
+                     ap, PTR, n, (int)K)
+  if (dtype == torch::kBFloat16) {
+    auto* op = (__hip_bfloat16*)out.data_ptr();
+    if (vec) LAUNCH_DQ(__hip_bfloat16, op, true); else LAUNCH_DQ(__hip_bfloat16, op, false);
+  } else {
+    auto* op = out.data_ptr<float>();
+    if (vec) LAUNCH_DQ(float, op, true); else LAUNCH_DQ(float, op, false);
+  }
+#undef LAUNCH_DQ
+  HIP_CHECK_LAST();
+  return out;
+}
+
+// ---------------------------------------------------------------------------
+// fused_fp8_gemm
+// ---------------------------------------------------------------------------
+
+// Swizzle on a byte offset within a [rows][128 B] image: the 16-byte chunk
+// index (bits 4..6) ^= (row>>1)&7 (bits 8..10).  An involution that keeps the
+// row, so the same function maps LDS byte -> source byte when staging and
+// logical byte -> LDS byte when reading.
+DEV_INLINE unsigned swz8(unsigned o) { return o ^ (((o >> 8) & 7u) << 4); }
+
+// Stage one [256][128 B] tile (32 KiB) into `image` via glds: 32 wave-level
+// 1-KiB pieces (8 full rows each), 4 per wave.  The LDS image is lane-linear
+// as glds requires; the per-lane GLOBAL source address carries the swizzle.
+// `gbase` is a byte pointer, `ld` the row pitch in bytes, `k0` a byte offset.
+DEV_INLINE void stage_tile_bytes(char* image, const char* gbase, long row0, long ld,
+                                 long k0, int wave, int lane) {
+#pragma unroll
+  for (int p4 = 0; p4 < 4; ++p4) {
+    const int piece = wave * 4 + p4;
+    const unsigned s = swz8(piece * 1024u + lane * 16u);  // source byte in tile
+    const char* src = gbase + (row0 + (s >> 7)) * ld + k0 + (s & 127u);
+    __builtin_amdgcn_global_load_lds(
+        (const __attribute__((address_space(1))) unsigned int*)src,
+        (__attribute__((address_space(3))) unsigned int*)(image) + (piece * 1024u) / 4,
+        16, 0, 0);
+  }
+}
+
+// fp8 A/B fragment of the 16x16x128 MFMA: chunks fq and 4+fq of `row`
+DEV_INLINE i32x8_q frag_fp8(const char* image, int row, int fq) {
+  const unsigned p = swz8((unsigned)row * 128u + (unsigned)fq * 16u);
+  const i32x4_q lo = *reinterpret_cast<const i32x4_q*>(image + p);
+  const i32x4_q hi = *reinterpret_cast<const i32x4_q*>(image + (p ^ 64u));
+  return i32x8_q{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+}
+
+// bf16 fragment (16x16x32 layout: lane -> row l&15, 8 k at ks*32 + (l>>4)*8)
+DEV_INLINE bf16x8_q frag_bf16(const char* image, int row, int ks, int fq) {
+  const unsigned o = (unsigned)row * 128u + (unsigned)ks * 64u + (unsigned)fq * 16u;
+  return *reinterpret_cast<const bf16x8_q*>(image + swz8(o));
+}
+
+#define FP8_TILE_BYTES (256 * 128)
+#define FP8_BUF_A(b) (smem + (b) * (2 * FP8_TILE_BYTES))
+#define FP8_BUF_B(b) (smem + (b) * (2 * FP8_TILE_BYTES) + FP8_TILE_BYTES)
+
+__global__ __launch_bounds__(512) void fused_fp8_gemm_kernel(
+    const uint8_t* __restrict__ xq,         // [M,K] e4m3 codes
+    const float* __restrict__ xa,           // [M] absmax of x rows
+    const uint8_t* __restrict__ wq,         // [N,K] e4m3 codes
+    const float* __restrict__ wa,           // [N] absmax of W rows
+    const __hip_bfloat16* __restrict__ t,   // [M,r] or null (pre-scaled)
+    const __hip_bfloat16* __restrict__ bw,  // [N,r] or null
+    const __hip_bfloat16* __restrict__ bias,  // [N] or null
+    __hip_bfloat16* __restrict__ y,         // [M,N]
+    long M, long N, long K, int r) {
+  // one __shared__ array only (glds pipeline rule)
+  extern __shared__ __attribute__((aligned(16))) char smem[];  // [2][A | B] = 128 KiB
+
+  // XCD-aware blockIdx remap (bijective form), as in fused_lora_gemm
+  const int nwg = gridDim.x;
+  const int q8 = nwg >> 3, r8 = nwg & 7;
+  int wgid = blockIdx.x;
+  if (nwg >= 8) {
+    const int xcd = wgid & 7, pos = wgid >> 3;
+    wgid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + pos;
+  }
+  const int nbn = (int)(N >> 8);
+  const long m0 = (long)(wgid / nbn) << 8;
+  const long n0 = (long)(wgid % nbn) << 8;
+
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int wr = wave >> 2;   // 0..1: wave m-position (128 rows)
+  const int wc = wave & 3;    // 0..3: wave n-position (64 cols)
+  const int fr = lane & 15;   // fragment row / C column
+  const int fq = lane >> 4;   // fragment k-group / C row group
+
+  f32x4_q acc[8][4];
+#pragma unroll
+  for (int i = 0; i < 8; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_q{0.f, 0.f, 0.f, 0.f};
+
+  // buffer b: A image at smem + b*64 KiB, B image 32 KiB behind it
+  const char* xg = (const char*)xq;
+  const char* wg = (const char*)wq;
+
+  const int KT = (int)(K >> 7);  // 128-k tiles
+  stage_tile_bytes(FP8_BUF_A(0), xg, m0, K, 0, wave, lane);
+  stage_tile_bytes(FP8_BUF_B(0), wg, n0, K, 0, wave, lane);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+
+  for (int kt = 0; kt < KT; ++kt) {
+    const int cur = kt & 1;
+    if (kt + 1 < KT) {
+      stage_tile_bytes(FP8_BUF_A(cur ^ 1), xg, m0, K, (long)(kt + 1) << 7, wave, lane);
+      stage_tile_bytes(FP8_BUF_B(cur ^ 1), wg, n0, K, (long)(kt + 1) << 7, wave, lane);
+    }
+    const char* A = FP8_BUF_A(cur);
+    const char* B = FP8_BUF_B(cur);
+    __builtin_amdgcn_s_setprio(1);
+    // the 4 B fragments stay resident (32 VGPRs); A fragments stream through
+    i32x8_q bf[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) bf[j] = frag_fp8(B, wc * 64 + j * 16 + fr, fq);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const i32x8_q af = frag_fp8(A, wr * 128 + i * 16 + fr, fq);
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
+            af, bf[j], acc[i][j], 0 /*A e4m3*/, 0 /*B e4m3*/, 0, 0, 0, 0);
+    }
+    __builtin_amdgcn_s_setprio(0);
+    // drain next tile's glds, then release the buffers we just read
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+  }
+
+  // ---- 1. rank-1 scales on the resident accumulators (fp32) --------------
+  {
+    float sw[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      sw[j] = __fdiv_rn(wa[n0 + wc * 64 + j * 16 + fr], FP8_MAX);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const f32x4_q ax =
+          *reinterpret_cast<const f32x4_q*>(xa + m0 + wr * 128 + i * 16 + fq * 4);
+      const f32x4_q sx = {__fdiv_rn(ax[0], FP8_MAX), __fdiv_rn(ax[1], FP8_MAX),
+                          __fdiv_rn(ax[2], FP8_MAX), __fdiv_rn(ax[3], FP8_MAX)};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[i][j] = acc[i][j] * (sx * sw[j]);
+    }
+  }
+
+  // ---- 2. LoRA rank-r update: acc += t_s-tile @ Bw-tile^T (bf16 MFMA) -----
+  if (r > 0) {
+    const int RC = r >> 6;  // [256][64] bf16 chunks per operand
+    const long ldr = (long)r * 2;
+#pragma unroll 1
+    for (int c = 0; c < RC; ++c) {
+      stage_tile_bytes(FP8_BUF_A(c & 1), (const char*)t, m0, ldr, (long)c << 7, wave, lane);
+      stage_tile_bytes(FP8_BUF_B(c & 1), (const char*)bw, n0, ldr, (long)c << 7, wave, lane);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+      const char* A = FP8_BUF_A(c & 1);
+      const char* B = FP8_BUF_B(c & 1);
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) {
+        bf16x8_q bfr[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) bfr[j] = frag_bf16(B, wc * 64 + j * 16 + fr, ks, fq);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          const bf16x8_q afr = frag_bf16(A, wr * 128 + i * 16 + fr, ks, fq);
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afr, bfr[j], acc[i][j],
+                                                                0, 0, 0);
+        }
+      }
+      __builtin_amdgcn_s_setprio(0);
+      __syncthreads();
+    }
+  }
+
+  // ---- 3+4. bias, one bf16 rounding, b128 row stores through LDS ----------
+  __syncthreads();
+  __bf16* mine = (__bf16*)smem + wave * (128 * 64);  // 16 KiB per wave
+#pragma unroll
+  for (int i = 0; i < 8; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        const int row = i * 16 + fq * 4 + reg;  // within wave tile
+        const int col = j * 16 + fr;
+        float v = acc[i][j][reg];
+        if (bias) v += (float)bias[n0 + wc * 64 + col];
+        mine[row * 64 + col] = (__bf16)v;
+      }
+  // no barrier needed: each wave reads only its own region
+#pragma unroll
+  for (int rr = 0; rr < 16; ++rr) {
+    const int row = rr * 8 + (lane >> 3);          // 0..127
+    const int cb = (lane & 7) * 8;                 // 8-col chunk
+    const bf16x8_q vv = *reinterpret_cast<const bf16x8_q*>(mine + row * 64 + cb);
+    *reinterpret_cast<bf16x8_q*>(y + (m0 + wr * 128 + row) * N + n0 + wc * 64 + cb) = vv;
+  }
+}
+
+// codes [rows*k] uint8 and absmax [rows] fp32, both contiguous, on x's device
+static void check_fp8_operand(const char* fn, const char* what, const torch::Tensor& q,
+                              const torch::Tensor& a, const torch::Device& dev, long rows,
+                              long k) {
+  TORCH_CHECK(q.is_cuda() && q.device() == dev, fn, ": ", what, " codes must be on xq's GPU");
+  TORCH_CHECK(q.scalar_type() == torch::kUInt8, fn, ": ", what, " codes must be uint8");
+  TORCH_CHECK(q.is_contiguous(), fn, ": ", what, " codes must be contiguous");
+  TORCH_CHECK(q.numel() == rows * k, fn, ": ", what, " codes must hold rows*K values");
+  TORCH_CHECK(a.device() == dev, fn, ": ", what, " absmax must be on xq's device");
+  TORCH_CHECK(a.scalar_type() == torch::kFloat32, fn, ": ", what, " absmax must be fp32");
+  TORCH_CHECK(a.is_contiguous(), fn, ": ", what, " absmax must be contiguous");
+  TORCH_CHECK(a.numel() == rows, fn, ": ", what, " absmax must hold one value per row");
+}
+
+static void check_fp8_bf16(const char* fn, const char* what, const torch::Tensor& v,
+                           const torch::Device& dev) {
+  TORCH_CHECK(v.device() == dev, fn, ": ", what, " must be on xq's device");
+  TORCH_CHECK(v.scalar_type() == torch::kBFloat16, fn, ": ", what, " must be bf16");
+  TORCH_CHECK(v.is_contiguous(), fn, ": ", what, " must be contiguous");
+}
+
+// xs / ws are the per-row absmax as quantize_rows_fp8 returns them; the
+// kernel turns them into scales (absmax/448) itself.
+torch::Tensor fused_fp8_gemm(torch::Tensor xq, torch::Tensor xs, torch::Tensor wq,
+                             torch::Tensor ws, long N, torch::Tensor t, torch::Tensor bw,
+                             torch::Tensor bias, double lora_scale) {
+  const char* fn = "fused_fp8_gemm";
+  TORCH_CHECK(xq.is_cuda(), fn, ": xq must be a GPU tensor");
+  TORCH_CHECK(xq.dim() == 2, fn, ": xq must be 2-D [M, K]");
+  const long M = xq.size(0), K = xq.size(1);
+  TORCH_CHECK(M > 0 && K > 0 && N > 0, fn, ": M, N and K must be > 0");
+  TORCH_CHECK(M % 256 == 0 && N % 256 == 0 && K % 128 == 0, fn,
+              " requires M%256==0, N%256==0, K%128==0");
+  const auto dev = xq.device();
+  check_fp8_operand(fn, "x", xq, xs, dev, M, K);
+  check_fp8_operand(fn, "w", wq, ws, dev, N, K);
+  int r = 0;
+  torch::Tensor t_scaled;
+  if (t.defined() && t.numel() > 0) {
+    check_fp8_bf16(fn, "t", t, dev);
+    TORCH_CHECK(t.dim() == 2 && t.size(0) == M, fn, ": t must be [M, r]");
+    r = (int)t.size(1);
+    TORCH_CHECK(t.size(1) % 64 == 0 && t.size(1) <= 256, fn,
+                ": r must be a multiple of 64, <= 256");
+    TORCH_CHECK(bw.defined(), fn, ": bw is required with t");
+    check_fp8_bf16(fn, "bw", bw, dev);
+    TORCH_CHECK(bw.dim() == 2 && bw.size(0) == N && bw.size(1) == r, fn,
+                ": bw must be [N, r]");
+    // fold the LoRA scale into t, as the other fused GEMMs do
+    t_scaled = (lora_scale == 1.0) ? t : (t * lora_scale).contiguous();
+  }
+  const __hip_bfloat16* bias_p = nullptr;
+  if (bias.defined() && bias.numel() > 0) {
+    check_fp8_bf16(fn, "bias", bias, dev);
+    TORCH_CHECK(bias.numel() == N, fn, ": bias must have N elements");
+    bias_p = (const __hip_bfloat16*)bias.data_ptr();
+  }
+  auto y = torch::empty({M, N}, xq.options().dtype(torch::kBFloat16));
+  auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
+  dim3 grid((unsigned)((M >> 8) * (N >> 8))), block(512);
+  const size_t smem = 4 * FP8_TILE_BYTES;  // 128 KiB
+  hipLaunchKernelGGL(fused_fp8_gemm_kernel, grid, block, smem, stream,
+                     xq.data_ptr<uint8_t>(), xs.data_ptr<float>(), wq.data_ptr<uint8_t>(),
+                     ws.data_ptr<float>(),
+                     r > 0 ? (const __hip_bfloat16*)t_scaled.data_ptr() : nullptr,
+                     r > 0 ? (const __hip_bfloat16*)bw.data_ptr() : nullptr, bias_p,
+                     (__hip_bfloat16*)y.data_ptr(), M, N, K, r);
+  HIP_CHECK_LAST();
+  return y;
+}
+
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma clang attribute pop
+#endif

@@ -801,8 +801,9 @@ class _FusedLoRALinear(torch.autograd.Function):
 
 
 class _QuantizedLoRALinear(torch.autograd.Function):
-    """K15 path: frozen W stays NF4/int8-packed end to end.  Forward runs
-    the dequant-fused MFMA GEMM (aligned NF4 shapes) or a transient
+    """K15 path: frozen W stays NF4/int8/fp8-packed end to end.  Forward runs
+    the dequant-fused MFMA GEMM (aligned NF4/int8 shapes), the fp8-code GEMM
+    on per-row quantised activations (aligned fp8 shapes) or a transient
     materialize; backward re-dequantizes transiently for dX.  Unlike the
     dense path, NO dense [N,K] W is ever saved for backward — the HBM
     footprint of the frozen weights stays at the packed size (the entire
@@ -830,7 +831,16 @@ class _QuantizedLoRALinear(torch.autograd.Function):
                    and r <= 256 and _FUSED_K1 != "0")
         fused_nf4 = aligned and qw.mode == "4bit" and K % 64 == 0
         fused_i8 = aligned and qw.mode == "8bit" and K % 256 == 0
-        if fused_nf4:
+        fused_fp8 = aligned and qw.mode == "fp8" and K % 128 == 0
+        if fused_fp8:
+            # activations quantised per token row, GEMM on the e4m3 codes;
+            # the unaligned arm below multiplies bf16 activations instead
+            xq, xs = hip.ext().quantize_rows_fp8(x2d)
+            y = hip.ext().fused_fp8_gemm(
+                xq, xs, qw.qdata, qw.absmax, N, t_u, lora_B,
+                bias if bias is not None else empty, scale)
+            del xq, xs
+        elif fused_nf4:
             y = hip.ext().fused_nf4_gemm(
                 x2d, qw.qdata, qw.absmax, N, t_u, lora_B,
                 bias if bias is not None else empty, scale)

@@ -1,4 +1,4 @@
-"""Blockwise frozen-weight quantization (K15): NF4 and int8.
+"""Frozen-weight quantization (K15): blockwise NF4 and int8, row-wise fp8.
 
 MI355X-native replacement for the reference's bitsandbytes usage
 (reference relora.py:225-238, 277-299): the frozen `W` of a wrapped Linear
@@ -6,6 +6,11 @@ lives quantized at rest (4-bit NF4 with fp32 absmax per 64-element block,
 or symmetric linear int8 per 256-element block) and is dequantized into a
 transient bf16 buffer for each GEMM; the ReLoRA merge runs
 dequant -> W += s·BA -> requant (the reference's exact flow).
+
+`fp8` stores OCP e4m3 codes with one fp32 absmax per output row; on aligned
+shapes its forward GEMM runs on the codes themselves (f8f6f4 matrix
+instructions, relora_amd/ops/csrc/fp8_gemm.hip) with the activations
+quantised per token row.
 
 GPU path: relora_amd/ops/csrc/quantize.hip.  The pure-python reference
 implementations here are the CPU path and the kernels' numerics oracle.
@@ -74,8 +79,32 @@ def dequantize_int8_ref(q, absmax, n, dtype=torch.float32):
     return out.to(dtype)
 
 
+FP8_MAX = 448.0  # largest finite e4m3fn value
+
+
+def quantize_fp8_ref(x):
+    """python oracle: x [R, K] -> (e4m3 codes uint8 [R, K], absmax fp32 [R]).
+
+    Per row: inv = 448/absmax (one fp32 division), code = e4m3_rne(v*inv)
+    with the product in fp32; a row of zeros gives zero codes."""
+    v = x.detach().float()
+    absmax = v.abs().amax(dim=1)
+    # a tensor numerator: `448.0 / absmax` would be reciprocal-then-multiply,
+    # two roundings where the format asks for one division
+    inv = torch.where(absmax > 0, torch.full_like(absmax, FP8_MAX) / absmax,
+                      torch.zeros_like(absmax))
+    codes = (v * inv.unsqueeze(1)).to(torch.float8_e4m3fn).view(torch.uint8)
+    return codes.contiguous(), absmax
+
+
+def dequantize_fp8_ref(codes, absmax, dtype=torch.float32):
+    """value = float(code) * (absmax/448) in fp32, rounded once to `dtype`."""
+    v = codes.view(torch.float8_e4m3fn).float() * (absmax.float() / FP8_MAX).unsqueeze(1)
+    return v.to(dtype)
+
+
 class QuantizedWeight(nn.Module):
-    """A frozen 2-D weight stored blockwise-quantized.
+    """A frozen 2-D weight stored quantized (blockwise NF4/int8, row-wise fp8).
 
     Quantization happens on first materialization on a CUDA device (CPU
     keeps the python reference path for tests).  `materialize()` returns a
@@ -85,7 +114,7 @@ class QuantizedWeight(nn.Module):
 
     def __init__(self, weight, mode):
         super().__init__()
-        if mode not in ("4bit", "8bit"):
+        if mode not in ("4bit", "8bit", "fp8"):
             raise ValueError(f"unknown quantize mode {mode!r}")
         self.mode = mode
         self.out_features, self.in_features = weight.shape
@@ -94,7 +123,15 @@ class QuantizedWeight(nn.Module):
         self._encode(weight.detach())
 
     def _encode(self, w):
-        if w.is_cuda:
+        if self.mode == "fp8":
+            # qdata uint8 [N*K], absmax fp32 [N]: same buffer names as the
+            # blockwise modes, so casts and checkpoints treat them alike
+            if w.is_cuda:
+                q, absmax = hip.ext().quantize_rows_fp8(w.contiguous().to(torch.bfloat16))
+            else:
+                q, absmax = quantize_fp8_ref(w)
+            q = q.view(-1)
+        elif w.is_cuda:
             wc = w.contiguous().to(torch.bfloat16)
             if self.mode == "4bit":
                 q, absmax = hip.ext().quantize_nf4(wc.view(-1))
@@ -110,7 +147,14 @@ class QuantizedWeight(nn.Module):
 
     def materialize(self, dtype=None):
         dtype = dtype or self.dtype
-        if self.qdata.is_cuda:
+        if self.mode == "fp8":
+            N, K = self.out_features, self.in_features
+            if self.qdata.is_cuda:
+                tdtype = torch.bfloat16 if dtype in (torch.bfloat16, torch.float16) else torch.float32
+                flat = hip.ext().dequantize_rows_fp8(self.qdata, self.absmax, N, K, tdtype)
+            else:
+                flat = dequantize_fp8_ref(self.qdata.view(N, K), self.absmax, dtype)
+        elif self.qdata.is_cuda:
             tdtype = torch.bfloat16 if dtype in (torch.bfloat16, torch.float16) else torch.float32
             if self.mode == "4bit":
                 flat = hip.ext().dequantize_nf4(self.qdata, self.absmax, self.numel, tdtype)
@@ -136,9 +180,15 @@ class QuantizedWeight(nn.Module):
 # absmax must survive model-wide dtype casts (a .to(bf16) on the model would
 # otherwise downcast the fp32 scales)
 def _quantized_apply(self, fn, recurse=True):
+    before = self.absmax
     out = nn.Module._apply(self, fn, recurse)
     if self.absmax.dtype != torch.float32:
-        self.absmax = self.absmax.float()
+        if self.mode == "fp8":
+            # a row scale rounded to bf16 would move the whole row: put the
+            # fp32 values back instead of widening the rounded ones
+            self.absmax = before.to(self.absmax.device)
+        else:
+            self.absmax = self.absmax.float()
     return out
 
 

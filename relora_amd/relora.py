@@ -16,7 +16,9 @@ MI355X notes:
 * the 4-bit/8-bit quantized frozen-W path replaces bitsandbytes with our
   blockwise NF4/int8 HIP kernels (relora_amd/ops/quant.py,
   ops/csrc/quantize.hip): W lives quantized at rest, dequantizes per GEMM,
-  and the merge runs dequant -> += BA·s -> requant.
+  and the merge runs dequant -> += BA·s -> requant;
+* `quantize="fp8"` stores e4m3 codes with one scale per output row and, on
+  aligned shapes, multiplies on the codes directly (ops/csrc/fp8_gemm.hip).
 """
 
 import json
@@ -224,8 +226,9 @@ class ReLoRaLinear(nn.Module):
         super().__init__()
         if r <= 0:
             raise ValueError("LoRA rank r must be >= 1; for a rank-0 (plain) layer just skip the ReLoRA wrap.")
-        if quantize not in (None, "4bit", "8bit"):
-            raise ValueError(f"quantize must be None, '4bit' or '8bit', got {quantize!r}")
+        if quantize not in (None, "4bit", "8bit", "fp8"):
+            raise ValueError(
+                f"quantize must be None, '4bit', '8bit' or 'fp8', got {quantize!r}")
 
         if lora_only:
             self.weight = None

@@ -244,6 +244,9 @@ if __name__ == "__main__":
         row0s=range(0, 128, 16), k0s=(0, 32)), "read_b128")
     print(f"lora tr64 writes: {'conflict-free' if pt_ok else f'{pt_w}-way'};  "
           f"reads: {'conflict-free' if rd_ok else f'{rd_w}-way'}")
+    import lds_bank_model as _self  # the fp8 patterns are defined further down
+    f8_ok, f8_w = verify(_self.fp8_gemm_frag_reads(), "read_b128")
+    print(f"fp8_gemm fragment reads: {'conflict-free' if f8_ok else f'{f8_w}-way'}")
 
 
 # ---------------------------------------------------------------------------
@@ -331,3 +334,30 @@ def perm16(row, grp):
 def transq_elem_16deep(row, k, ldt=128):
     """TRANSQ tile element for 256-byte-stride rows (r=128)."""
     return row * ldt + perm16(row, (k & 127) >> 3) * 8 + (k & 7)
+
+
+# ---------------------------------------------------------------------------
+# fp8_gemm.hip: [256][128 B] operand images, 16-byte chunk ^= (row>>1)&7.
+# fp8 fragments (16x16x128): lane (fr, fq) reads chunks fq and 4+fq of row fr
+# with two b128 reads; the bf16 LoRA fragments (16x16x32) read chunk ks*4+fq.
+# ---------------------------------------------------------------------------
+
+def fp8_gemm_swz(o):
+    return o ^ (((o >> 8) & 7) << 4)
+
+
+def fp8_gemm_frag_reads(row0s=range(0, 256, 16)):
+    """every b128 fragment read of fused_fp8_gemm: chunks 0..7 of 16 rows."""
+    for row0 in row0s:
+        for hi in range(2):          # fp8: second read is chunk 4+fq
+            yield {l: fp8_gemm_swz((row0 + (l & 15)) * 128 + (hi * 4 + (l >> 4)) * 16)
+                   for l in range(64)}
+        for ks in range(2):          # bf16: chunk ks*4+fq — the same address set
+            yield {l: fp8_gemm_swz((row0 + (l & 15)) * 128 + ks * 64 + (l >> 4) * 16)
+                   for l in range(64)}
+
+
+def fp8_gemm_stage_sources(piece):
+    """glds staging of one 1-KiB piece: LDS byte (lane-linear) -> source byte
+    of the tile; must be a permutation of the piece's own 8 rows."""
+    return [fp8_gemm_swz(piece * 1024 + lane * 16) for lane in range(64)]
