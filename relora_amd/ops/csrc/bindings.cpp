@@ -117,6 +117,13 @@ torch::Tensor dequantize_rows_fp8(torch::Tensor q, torch::Tensor absmax, long R,
 torch::Tensor fused_fp8_gemm(torch::Tensor xq, torch::Tensor xs, torch::Tensor wq,
                              torch::Tensor ws, long N, torch::Tensor t, torch::Tensor bw,
                              torch::Tensor bias, double lora_scale);
+// mxfp4_gemm.hip
+std::vector<torch::Tensor> quantize_rows_mxfp4(torch::Tensor x);
+torch::Tensor dequantize_rows_mxfp4(torch::Tensor codes, torch::Tensor scales, long R, long K,
+                                    torch::ScalarType dtype);
+torch::Tensor fused_mxfp4_gemm(torch::Tensor xq, torch::Tensor xs, torch::Tensor wq,
+                               torch::Tensor wscales, long N, torch::Tensor t,
+                               torch::Tensor bw, torch::Tensor bias, double lora_scale);
 // attention.hip
 std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor v,
                                     double scale, c10::optional<torch::Tensor> doc_start);
@@ -218,6 +225,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fused_fp8_gemm", &fused_fp8_gemm,
         "y = (xq@wq^T)*sx*sw^T (+bias) + s*t@Bw^T on the f8f6f4 MFMA, 256^2 glds tile (gfx950)",
         py::arg("xq"), py::arg("xs"), py::arg("wq"), py::arg("ws"), py::arg("N"),
+        py::arg("t"), py::arg("bw"), py::arg("bias"), py::arg("lora_scale"));
+  m.def("quantize_rows_mxfp4", &quantize_rows_mxfp4,
+        "bf16 [R,K] -> (e2m1 codes uint8 [R,Kp/2], E8M0 scales uint8 [R,Kp/32]), OCP MX "
+        "blocks of 32 along K (gfx950)");
+  m.def("dequantize_rows_mxfp4", &dequantize_rows_mxfp4,
+        "MXFP4 codes + block scales -> bf16/fp32 [R,K] (gfx950)");
+  // xq / xs: quantize_rows_fp8 of the activations; wq / wscales: quantize_rows_mxfp4 of W
+  m.def("fused_mxfp4_gemm", &fused_mxfp4_gemm,
+        "y = (xq@W4^T)*sx (+bias) + s*t@Bw^T, e4m3 x MXFP4 on the block-scaled f8f6f4 MFMA, "
+        "256^2 glds tile (gfx950)",
+        py::arg("xq"), py::arg("xs"), py::arg("wq"), py::arg("wscales"), py::arg("N"),
         py::arg("t"), py::arg("bw"), py::arg("bias"), py::arg("lora_scale"));
   // doc_start: optional int32 [B, S] intra-document mask (padded head_dim <= 64)
   m.def("attn_fwd", &attn_fwd, "causal flash attention forward (gfx950 MFMA)",

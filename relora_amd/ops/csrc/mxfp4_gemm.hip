@@ -1,0 +1,559 @@
+// Some packed-fp32 instruction forms miscompute on this target, so this file
+// is compiled without them (as fp8_gemm.hip; the attribute has to cover the
+// headers too, or their helpers are not inlined and the accumulators spill).
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma clang attribute push(__attribute__((target("no-packed-fp32-ops"))), apply_to = function)
+#endif
+#include "hip/hip_runtime.h"
+// MXFP4 frozen-W path (`--quantize mxfp4`) on the gfx950 block-scaled matrix
+// cores.
+//
+// Format (ops/quant.py quantize_mxfp4_ref is the definition): OCP MX, a block
+// is 32 consecutive k of one row of W [N,K].  Per block one E8M0 scale byte
+//   byte = clamp(E - 2, 0, 254),  E = biased fp32 exponent field of amax
+// (127 for an all-zero block), so amax * 2^(127-byte) lies in [4, 8); per
+// element one e2m1 code (sign in bit 3, magnitudes 0 .5 1 1.5 2 3 4 6) of
+// v * 2^(127-byte), rounded to nearest with ties to the even code, saturating
+// at 6.  The sign bit of v is always kept (so -0 and values that round to
+// zero encode as code 8).  Two codes a byte, the LOW nibble is the lower k.
+// codes uint8 [N, Kp/2], scales uint8 [N, Kp/32], Kp = K rounded up to 32;
+// padding of a short last block encodes as zero codes.
+// value = e2m1(code) * 2^(byte-127).
+//
+//   quantize_rows_mxfp4    bf16 [R,K] -> (codes, scales)
+//   dequantize_rows_mxfp4  codes, scales -> bf16 | fp32 [R,K]
+//   fused_mxfp4_gemm       y = (xq·W4^T)·sx (+bias) + s·t·Bw^T, bf16 out,
+//                          xq/xs from quantize_rows_fp8, W4 as stored
+//
+// GEMM structure: fused_fp8_gemm's 256x256 tile, 8 waves (2M x 4N),
+// double-buffered global_load_lds staging, XCD remap and one vmcnt(0) +
+// barrier per 128-k tile, with what the format changes:
+//   * v_mfma_scale_f32_16x16x128_f8f6f4 with A = e4m3 (cbsz 0), B = e2m1
+//     (blgp 4) and a per-lane E8M0 scale on B; A's scale is the constant 127.
+//   * Lane-to-k assignment, as the read-back test found it on the hardware:
+//     a 4-bit operand's lane (fr, fq) holds k = 32*fq .. 32*fq+31 in its 4
+//     dwords, low nibble first, and its scale byte covers exactly those 32 k
+//     (one MX block); an 8-bit operand's lane holds k = 16*fq .. +15 in
+//     dwords 0-3 and k = 64+16*fq .. +15 in dwords 4-7.  So the e2m1 lane
+//     reads the 16-byte chunk fq of its 64-byte row, and the e4m3 lane the
+//     chunks fq and 4+fq of its 128-byte row: fp8_gemm's assignment is the
+//     hardware's own order, and its swizzle (chunk ^= (row>>1)&7) carries
+//     over to the A image and to the bf16 LoRA fragments that reuse it.  The
+//     B image is 2-way conflicted when linear (rows 0-3 and 12-15 of a b128
+//     service group share bank slots); chunk ^= 2*row[3] makes it
+//     conflict-free in tools/lds_bank_model.py (mxfp4_gemm_b_frag_reads).
+//   * The B tile is 16 KiB, the double buffer 96 KiB; a B fragment is 4
+//     dwords, the four resident ones cost 16 VGPRs.
+//   * Scales: one dword per (W row, K-tile) holds the tile's four block
+//     bytes.  A lane loads the dwords of its 4 column fragments one tile
+//     ahead (L2 hits) and shifts byte fq down itself, since the instruction's
+//     byte selector is an immediate.
+// Epilogue as fused_fp8_gemm: acc * xs[m]/448 (no W row scale), the rank-r
+// bf16 MFMA update on the same accumulators, bias, one rounding to bf16, b128
+// row stores through LDS (in two 64-row halves: 96 KiB hold 8 x 8 KiB).
+
+#include <ATen/hip/HIPContext.h>
+#include <torch/extension.h>
+
+#include "common.h"
+
+typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_m;
+typedef __attribute__((ext_vector_type(4))) float f32x4_m;
+typedef __attribute__((ext_vector_type(4))) int i32x4_m;
+typedef __attribute__((ext_vector_type(8))) int i32x8_m;
+
+#define MX_BLOCK 32
+#define E4M3_MAX 448.0f
+
+// ---------------------------------------------------------------------------
+// Quantiser / dequantiser
+// ---------------------------------------------------------------------------
+
+// scale byte of a block from its amax (>= 0)
+DEV_INLINE unsigned mx_scale_byte(float amax) {
+  if (!(amax > 0.f)) return 127u;
+  const int e = (int)((__float_as_uint(amax) >> 23) & 0xffu) - 2;
+  return (unsigned)min(max(e, 0), 254);
+}
+
+// 2^(127-byte): a normal fp32 for every byte mx_scale_byte returns (<= 253)
+DEV_INLINE float mx_inv_scale(unsigned byte) { return __uint_as_float((254u - byte) << 23); }
+
+// 2^(byte-127); byte 0 is the fp32 subnormal 2^-127
+DEV_INLINE float mx_scale(unsigned byte) {
+  return __uint_as_float(byte ? byte << 23 : 0x00400000u);
+}
+
+// e2m1 code of s (already scaled): RNE on the magnitude grid, ties to the
+// even code, saturating; the sign bit of s is kept.
+DEV_INLINE unsigned e2m1_encode(float s) {
+  const float a = fabsf(s);
+  const unsigned m = (a > 0.25f) + (a >= 0.75f) + (a > 1.25f) + (a >= 1.75f) + (a > 2.5f) +
+                     (a >= 3.5f) + (a > 5.0f);
+  return m | ((__float_as_uint(s) >> 28) & 8u);
+}
+
+DEV_INLINE float e2m1_decode(unsigned c) {
+  const unsigned m = c & 7u;
+  const float mag = m < 2u ? 0.5f * (float)m
+                           : __uint_as_float((((m >> 1) + 126u) << 23) | ((m & 1u) << 22));
+  return (c & 8u) ? -mag : mag;
+}
+
+// K % 32 == 0: four lanes per block, 8 bf16 (one 16-byte load) per lane, the
+// block max by two shuffles, one dword of 8 codes per lane; consecutive lanes
+// load and store consecutive memory.  n8 = R*K/8 lanes.
+__global__ __launch_bounds__(256) void quantize_rows_mxfp4_kernel(
+    const __hip_bfloat16* __restrict__ x, uint8_t* __restrict__ codes,
+    uint8_t* __restrict__ scales, long n8) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  const bool live = i < n8;  // n8 % 4 == 0: a 4-lane group is live or dead as one
+  const uint4 u = live ? reinterpret_cast<const uint4*>(x)[i] : make_uint4(0, 0, 0, 0);
+  const unsigned w[4] = {u.x, u.y, u.z, u.w};
+  float v[8];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    v[2 * j] = __uint_as_float(w[j] << 16);
+    v[2 * j + 1] = __uint_as_float(w[j] & 0xffff0000u);
+  }
+  float am = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) am = fmaxf(am, fabsf(v[j]));
+  am = fmaxf(am, __shfl_xor(am, 1));
+  am = fmaxf(am, __shfl_xor(am, 2));
+  if (!live) return;
+  const unsigned byte = mx_scale_byte(am);
+  const float inv = mx_inv_scale(byte);
+  unsigned packed = 0;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) packed |= e2m1_encode(__fmul_rn(v[j], inv)) << (4 * j);
+  reinterpret_cast<unsigned*>(codes)[i] = packed;
+  if ((i & 3) == 0) scales[i >> 2] = (uint8_t)byte;
+}
+
+// any K (e.g. 5461): one thread per block, scalar loads, byte stores; the
+// last block of a row may be short, its padding gives zero codes.  Off the
+// hot path (once per merge).
+__global__ __launch_bounds__(256) void quantize_rows_mxfp4_any_kernel(
+    const __hip_bfloat16* __restrict__ x, uint8_t* __restrict__ codes,
+    uint8_t* __restrict__ scales, long nblocks, int K, int bpr) {
+  const long b = (long)blockIdx.x * 256 + threadIdx.x;
+  if (b >= nblocks) return;
+  const long row = b / bpr;
+  const int k0 = (int)(b % bpr) * MX_BLOCK;
+  const int len = min(MX_BLOCK, K - k0);
+  const __hip_bfloat16* src = x + row * K + k0;
+  float am = 0.f;
+  for (int k = 0; k < len; ++k) am = fmaxf(am, fabsf(to_f32(src[k])));
+  const unsigned byte = mx_scale_byte(am);
+  const float inv = mx_inv_scale(byte);
+  uint8_t* dst = codes + b * (MX_BLOCK / 2);
+  for (int k = 0; k < MX_BLOCK; k += 2) {
+    const unsigned lo = k < len ? e2m1_encode(__fmul_rn(to_f32(src[k]), inv)) : 0u;
+    const unsigned hi = k + 1 < len ? e2m1_encode(__fmul_rn(to_f32(src[k + 1]), inv)) : 0u;
+    dst[k >> 1] = (uint8_t)(lo | (hi << 4));
+  }
+  scales[b] = (uint8_t)byte;
+}
+
+std::vector<torch::Tensor> quantize_rows_mxfp4(torch::Tensor x) {
+  const char* fn = "quantize_rows_mxfp4";
+  TORCH_CHECK(x.is_cuda(), fn, ": x must be a GPU tensor");
+  TORCH_CHECK(x.dim() == 2, fn, ": x must be 2-D [R, K]");
+  TORCH_CHECK(x.is_contiguous(), fn, ": x must be contiguous");
+  TORCH_CHECK(x.scalar_type() == torch::kBFloat16, fn, ": x must be bf16");
+  const long R = x.size(0), K = x.size(1);
+  TORCH_CHECK(R > 0 && K > 0, fn, ": R and K must be > 0");
+  TORCH_CHECK(K < (1L << 31) - MX_BLOCK && R < (1L << 31), fn, ": shape too large");
+  const long bpr = (K + MX_BLOCK - 1) / MX_BLOCK;  // blocks per row
+  auto codes = torch::empty({R, bpr * (MX_BLOCK / 2)}, x.options().dtype(torch::kUInt8));
+  auto scales = torch::empty({R, bpr}, x.options().dtype(torch::kUInt8));
+  auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
+  const auto* xp = (const __hip_bfloat16*)x.data_ptr();
+  if (K % MX_BLOCK == 0) {
+    const long n8 = R * K / 8;
+    hipLaunchKernelGGL(quantize_rows_mxfp4_kernel, dim3((unsigned)((n8 + 255) / 256)),
+                       dim3(256), 0, stream, xp, codes.data_ptr<uint8_t>(),
+                       scales.data_ptr<uint8_t>(), n8);
+  } else {
+    const long nblocks = R * bpr;
+    hipLaunchKernelGGL(quantize_rows_mxfp4_any_kernel,
+                       dim3((unsigned)((nblocks + 255) / 256)), dim3(256), 0, stream, xp,
+                       codes.data_ptr<uint8_t>(), scales.data_ptr<uint8_t>(), nblocks, (int)K,
+                       (int)bpr);
+  }
+  HIP_CHECK_LAST();
+  return {codes, scales};
+}
+
+// VEC (K % 32 == 0, so rows are dense in codes and scales): one thread per
+// dword of 8 codes.  Otherwise one thread per output element.
+template <typename T, bool VEC>
+__global__ __launch_bounds__(256) void dequantize_rows_mxfp4_kernel(
+    const uint8_t* __restrict__ codes, const uint8_t* __restrict__ scales,
+    T* __restrict__ out, long n, int K, int bpr) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (VEC) {
+    if (i >= n / 8) return;
+    const unsigned c = reinterpret_cast<const unsigned*>(codes)[i];
+    const float sc = mx_scale(scales[i >> 2]);
+    T v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = from_f32<T>(__fmul_rn(e2m1_decode(c >> (4 * j)), sc));
+    store8(out + i * 8, *reinterpret_cast<const Vec8<T>*>(v));
+  } else {
+    if (i >= n) return;
+    const long row = i / K;
+    const int k = (int)(i % K);
+    const unsigned c = codes[row * bpr * (MX_BLOCK / 2) + (k >> 1)] >> (4 * (k & 1));
+    out[i] = from_f32<T>(__fmul_rn(e2m1_decode(c), mx_scale(scales[row * bpr + k / MX_BLOCK])));
+  }
+}
+
+torch::Tensor dequantize_rows_mxfp4(torch::Tensor codes, torch::Tensor scales, long R, long K,
+                                    torch::ScalarType dtype) {
+  const char* fn = "dequantize_rows_mxfp4";
+  TORCH_CHECK(codes.is_cuda(), fn, ": codes must be a GPU tensor");
+  TORCH_CHECK(codes.scalar_type() == torch::kUInt8 && codes.is_contiguous(), fn,
+              ": codes must be contiguous uint8");
+  TORCH_CHECK(R > 0 && K > 0 && K < (1L << 31) - MX_BLOCK, fn, ": bad R or K");
+  const long bpr = (K + MX_BLOCK - 1) / MX_BLOCK;
+  TORCH_CHECK(codes.numel() == R * bpr * (MX_BLOCK / 2), fn,
+              ": codes must hold R*Kp/2 bytes (Kp = K rounded up to 32)");
+  TORCH_CHECK(scales.device() == codes.device() && scales.scalar_type() == torch::kUInt8 &&
+                  scales.is_contiguous() && scales.numel() == R * bpr,
+              fn, ": scales must be R*Kp/32 contiguous uint8 values on the codes' device");
+  TORCH_CHECK(dtype == torch::kBFloat16 || dtype == torch::kFloat32, fn,
+              ": output dtype must be bf16 or fp32");
+  auto out = torch::empty({R, K}, codes.options().dtype(dtype));
+  auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
+  const long n = R * K;
+  const bool vec = K % MX_BLOCK == 0;
+  const long threads = vec ? n / 8 : n;
+  dim3 grid((unsigned)((threads + 255) / 256)), block(256);
+  const uint8_t* cp = codes.data_ptr<uint8_t>();
+  const uint8_t* sp = scales.data_ptr<uint8_t>();
+#define LAUNCH_DQ(T, PTR, V)                                                           \
+  hipLaunchKernelGGL((dequantize_rows_mxfp4_kernel<T, V>), grid, block, 0, stream, cp, \
+                     sp, PTR, n, (int)K, (int)bpr)
+  if (dtype == torch::kBFloat16) {
+    auto* op = (__hip_bfloat16*)out.data_ptr();
+    if (vec) LAUNCH_DQ(__hip_bfloat16, op, true); else LAUNCH_DQ(__hip_bfloat16, op, false);
+  } else {
+    auto* op = out.data_ptr<float>();
+    if (vec) LAUNCH_DQ(float, op, true); else LAUNCH_DQ(float, op, false);
+  }
+#undef LAUNCH_DQ
+  HIP_CHECK_LAST();
+  return out;
+}
+
+// ---------------------------------------------------------------------------
+// fused_mxfp4_gemm
+// ---------------------------------------------------------------------------
+
+// Swizzles on a byte offset within an image; both keep the row and are
+// involutions, so one function maps LDS byte -> source byte when staging and
+// logical byte -> LDS byte when reading.
+// A-type image [rows][128 B]: 16-byte chunk (bits 4..6) ^= (row>>1)&7, as fp8_gemm
+DEV_INLINE unsigned swz_a(unsigned o) { return o ^ (((o >> 8) & 7u) << 4); }
+// B image [rows][64 B]: 16-byte chunk (bits 4..5) ^= 2*row[3]
+DEV_INLINE unsigned swz_b(unsigned o) { return o ^ (((o >> 9) & 1u) << 5); }
+
+// Stage one [256][128 B] tile (32 KiB) via glds: 32 wave-level 1-KiB pieces
+// (8 full rows each), 4 per wave.  The LDS image is lane-linear as glds
+// requires; the per-lane GLOBAL source address carries the swizzle.
+DEV_INLINE void stage_a_tile(char* image, const char* gbase, long row0, long ld, long k0,
+                             int wave, int lane) {
+#pragma unroll
+  for (int p4 = 0; p4 < 4; ++p4) {
+    const int piece = wave * 4 + p4;
+    const unsigned s = swz_a(piece * 1024u + lane * 16u);  // source byte in tile
+    const char* src = gbase + (row0 + (s >> 7)) * ld + k0 + (s & 127u);
+    __builtin_amdgcn_global_load_lds(
+        (const __attribute__((address_space(1))) unsigned int*)src,
+        (__attribute__((address_space(3))) unsigned int*)(image) + (piece * 1024u) / 4,
+        16, 0, 0);
+  }
+}
+
+// Stage one [256][64 B] e2m1 tile (16 KiB): 16 pieces of 16 full rows, 2 per wave
+DEV_INLINE void stage_b_tile(char* image, const char* gbase, long row0, long ld, long k0,
+                             int wave, int lane) {
+#pragma unroll
+  for (int p2 = 0; p2 < 2; ++p2) {
+    const int piece = wave * 2 + p2;
+    const unsigned s = swz_b(piece * 1024u + lane * 16u);
+    const char* src = gbase + (row0 + (s >> 6)) * ld + k0 + (s & 63u);
+    __builtin_amdgcn_global_load_lds(
+        (const __attribute__((address_space(1))) unsigned int*)src,
+        (__attribute__((address_space(3))) unsigned int*)(image) + (piece * 1024u) / 4,
+        16, 0, 0);
+  }
+}
+
+// e4m3 A fragment: k = 16*fq .. +15 and 64+16*fq .. +15 of `row` (chunks fq, 4+fq)
+DEV_INLINE i32x8_m frag_e4m3(const char* image, int row, int fq) {
+  const unsigned p = swz_a((unsigned)row * 128u + (unsigned)fq * 16u);
+  const i32x4_m lo = *reinterpret_cast<const i32x4_m*>(image + p);
+  const i32x4_m hi = *reinterpret_cast<const i32x4_m*>(image + (p ^ 64u));
+  return i32x8_m{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+}
+
+// e2m1 B fragment: the 32 codes k = 32*fq .. +31 of `row` (chunk fq)
+DEV_INLINE i32x4_m frag_e2m1(const char* image, int row, int fq) {
+  return *reinterpret_cast<const i32x4_m*>(image + swz_b((unsigned)row * 64u + (unsigned)fq * 16u));
+}
+
+// bf16 fragment of an A-type image (16x16x32: row l&15, 8 k at ks*32+(l>>4)*8)
+DEV_INLINE bf16x8_m frag_bf16_a(const char* image, int row, int ks, int fq) {
+  const unsigned o = (unsigned)row * 128u + (unsigned)ks * 64u + (unsigned)fq * 16u;
+  return *reinterpret_cast<const bf16x8_m*>(image + swz_a(o));
+}
+
+#define MX_A_BYTES (256 * 128)
+#define MX_B_BYTES (256 * 64)
+#define MX_BUF_A(b) (smem + (b) * (MX_A_BYTES + MX_B_BYTES))
+#define MX_BUF_B(b) (smem + (b) * (MX_A_BYTES + MX_B_BYTES) + MX_A_BYTES)
+#define MX_SMEM_BYTES (2 * (MX_A_BYTES + MX_B_BYTES))  // 96 KiB
+
+__global__ __launch_bounds__(512) void fused_mxfp4_gemm_kernel(
+    const uint8_t* __restrict__ xq,         // [M,K] e4m3 codes
+    const float* __restrict__ xa,           // [M] absmax of x rows
+    const uint8_t* __restrict__ wq,         // [N,K/2] e2m1 codes
+    const unsigned* __restrict__ wsc,       // [N,K/128] dwords of 4 E8M0 bytes
+    const __hip_bfloat16* __restrict__ t,   // [M,r] or null (pre-scaled)
+    const __hip_bfloat16* __restrict__ bw,  // [N,r] or null
+    const __hip_bfloat16* __restrict__ bias,  // [N] or null
+    __hip_bfloat16* __restrict__ y,         // [M,N]
+    long M, long N, long K, int r) {
+  // one __shared__ array only (glds pipeline rule)
+  extern __shared__ __attribute__((aligned(16))) char smem[];  // [2][A 32K | B 16K]
+
+  // XCD-aware blockIdx remap (bijective form), as in fused_lora_gemm
+  const int nwg = gridDim.x;
+  const int q8 = nwg >> 3, r8 = nwg & 7;
+  int wgid = blockIdx.x;
+  if (nwg >= 8) {
+    const int xcd = wgid & 7, pos = wgid >> 3;
+    wgid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + pos;
+  }
+  const int nbn = (int)(N >> 8);
+  const long m0 = (long)(wgid / nbn) << 8;
+  const long n0 = (long)(wgid % nbn) << 8;
+
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int wr = wave >> 2;   // 0..1: wave m-position (128 rows)
+  const int wc = wave & 3;    // 0..3: wave n-position (64 cols)
+  const int fr = lane & 15;   // fragment row / C column
+  const int fq = lane >> 4;   // fragment k-group (= MX block of the tile) / C row group
+
+  f32x4_m acc[8][4];
+#pragma unroll
+  for (int i = 0; i < 8; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_m{0.f, 0.f, 0.f, 0.f};
+
+  const char* xg = (const char*)xq;
+  const char* wg = (const char*)wq;
+  const long ldw = K >> 1;          // W row pitch in bytes
+  const int KT = (int)(K >> 7);     // 128-k tiles = scale dwords per W row
+  // this lane's 4 scale rows (one per column fragment), tile 0
+  const unsigned* srow = wsc + (n0 + wc * 64 + fr) * KT;
+  unsigned sc[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) sc[j] = srow[(long)j * 16 * KT];
+
+  stage_a_tile(MX_BUF_A(0), xg, m0, K, 0, wave, lane);
+  stage_b_tile(MX_BUF_B(0), wg, n0, ldw, 0, wave, lane);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+
+  for (int kt = 0; kt < KT; ++kt) {
+    const int cur = kt & 1;
+    unsigned nsc[4] = {0u, 0u, 0u, 0u};
+    if (kt + 1 < KT) {
+      stage_a_tile(MX_BUF_A(cur ^ 1), xg, m0, K, (long)(kt + 1) << 7, wave, lane);
+      stage_b_tile(MX_BUF_B(cur ^ 1), wg, n0, ldw, (long)(kt + 1) << 6, wave, lane);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) nsc[j] = srow[(long)j * 16 * KT + kt + 1];
+    }
+    const char* A = MX_BUF_A(cur);
+    const char* B = MX_BUF_B(cur);
+    __builtin_amdgcn_s_setprio(1);
+    // the 4 B fragments (16 VGPRs) and their block scales stay resident
+    i32x8_m bf[4];
+    int sb[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const i32x4_m b4 = frag_e2m1(B, wc * 64 + j * 16 + fr, fq);
+      bf[j] = i32x8_m{b4[0], b4[1], b4[2], b4[3], 0, 0, 0, 0};
+      sb[j] = (int)((sc[j] >> (8 * fq)) & 0xffu);  // byte fq -> byte 0 (op-sel 0)
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const i32x8_m af = frag_e4m3(A, wr * 128 + i * 16 + fr, fq);
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
+            af, bf[j], acc[i][j], 0 /*A e4m3*/, 4 /*B e2m1*/, 0, 127 /*A scale 2^0*/, 0, sb[j]);
+    }
+    __builtin_amdgcn_s_setprio(0);
+    // drain next tile's glds and scale loads, then release the buffers
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 4; ++j) sc[j] = nsc[j];
+  }
+
+  // ---- 1. activation row scale on the resident accumulators (fp32) -------
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const f32x4_m ax = *reinterpret_cast<const f32x4_m*>(xa + m0 + wr * 128 + i * 16 + fq * 4);
+    const f32x4_m sx = {__fdiv_rn(ax[0], E4M3_MAX), __fdiv_rn(ax[1], E4M3_MAX),
+                        __fdiv_rn(ax[2], E4M3_MAX), __fdiv_rn(ax[3], E4M3_MAX)};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = acc[i][j] * sx;
+  }
+
+  // ---- 2. LoRA rank-r update: acc += t_s-tile @ Bw-tile^T (bf16 MFMA) -----
+  // t and Bw chunks are [256][64] bf16 = A-type images at smem and smem+32K
+  if (r > 0) {
+    const int RC = r >> 6;
+    const long ldr = (long)r * 2;
+    char* TA = smem;
+    char* TB = smem + MX_A_BYTES;
+#pragma unroll 1
+    for (int c = 0; c < RC; ++c) {
+      stage_a_tile(TA, (const char*)t, m0, ldr, (long)c << 7, wave, lane);
+      stage_a_tile(TB, (const char*)bw, n0, ldr, (long)c << 7, wave, lane);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) {
+        bf16x8_m bfr[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) bfr[j] = frag_bf16_a(TB, wc * 64 + j * 16 + fr, ks, fq);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          const bf16x8_m afr = frag_bf16_a(TA, wr * 128 + i * 16 + fr, ks, fq);
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afr, bfr[j], acc[i][j],
+                                                                0, 0, 0);
+        }
+      }
+      __builtin_amdgcn_s_setprio(0);
+      __syncthreads();  // all waves done reading before the next chunk lands
+    }
+  }
+
+  // ---- 3+4. bias, one bf16 rounding, b128 row stores through LDS ----------
+  // each wave owns 8 KiB: its 128x64 tile goes out in two 64-row halves
+  __bf16* mine = (__bf16*)smem + wave * (64 * 64);
+  float bv[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) bv[j] = bias ? (float)bias[n0 + wc * 64 + j * 16 + fr] : 0.f;
+#pragma unroll
+  for (int half = 0; half < 2; ++half) {
+#pragma unroll
+    for (int i4 = 0; i4 < 4; ++i4)
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+          const int row = i4 * 16 + fq * 4 + reg;  // within the half
+          const int col = j * 16 + fr;
+          mine[row * 64 + col] = (__bf16)(acc[half * 4 + i4][j][reg] + bv[j]);
+        }
+    // no block barrier: a wave reads only its own region; keep the order
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int rr = 0; rr < 8; ++rr) {
+      const int row = rr * 8 + (lane >> 3);          // 0..63
+      const int cb = (lane & 7) * 8;                 // 8-col chunk
+      const bf16x8_m vv = *reinterpret_cast<const bf16x8_m*>(mine + row * 64 + cb);
+      *reinterpret_cast<bf16x8_m*>(y + (m0 + wr * 128 + half * 64 + row) * N + n0 + wc * 64 +
+                                   cb) = vv;
+    }
+    __builtin_amdgcn_wave_barrier();
+  }
+}
+
+static void check_mx_u8(const char* fn, const char* what, const torch::Tensor& v,
+                        const torch::Device& dev, long numel, const char* count) {
+  TORCH_CHECK(v.is_cuda() && v.device() == dev, fn, ": ", what, " must be on xq's GPU");
+  TORCH_CHECK(v.scalar_type() == torch::kUInt8, fn, ": ", what, " must be uint8");
+  TORCH_CHECK(v.is_contiguous(), fn, ": ", what, " must be contiguous");
+  TORCH_CHECK(v.numel() == numel, fn, ": ", what, " must hold ", count, " bytes");
+  // 16-byte glds pieces and the scale dwords: a byte-offset view would misalign them
+  TORCH_CHECK((uintptr_t)v.data_ptr() % 16 == 0, fn, ": ", what, " must be 16-byte aligned");
+}
+
+static void check_mx_bf16(const char* fn, const char* what, const torch::Tensor& v,
+                          const torch::Device& dev) {
+  TORCH_CHECK(v.device() == dev, fn, ": ", what, " must be on xq's device");
+  TORCH_CHECK(v.scalar_type() == torch::kBFloat16, fn, ": ", what, " must be bf16");
+  TORCH_CHECK(v.is_contiguous(), fn, ": ", what, " must be contiguous");
+}
+
+// xq / xs as quantize_rows_fp8 returns them (the kernel divides xs by 448);
+// wq / wscales as quantize_rows_mxfp4 returns them for a [N,K] weight.
+torch::Tensor fused_mxfp4_gemm(torch::Tensor xq, torch::Tensor xs, torch::Tensor wq,
+                               torch::Tensor wscales, long N, torch::Tensor t,
+                               torch::Tensor bw, torch::Tensor bias, double lora_scale) {
+  const char* fn = "fused_mxfp4_gemm";
+  TORCH_CHECK(xq.is_cuda(), fn, ": xq must be a GPU tensor");
+  TORCH_CHECK(xq.dim() == 2, fn, ": xq must be 2-D [M, K]");
+  const long M = xq.size(0), K = xq.size(1);
+  TORCH_CHECK(M > 0 && K > 0 && N > 0, fn, ": M, N and K must be > 0");
+  TORCH_CHECK(M % 256 == 0 && N % 256 == 0 && K % 128 == 0, fn,
+              " requires M%256==0, N%256==0, K%128==0");
+  TORCH_CHECK(M * N < (1L << 40) && K < (1L << 31), fn, ": shape too large");
+  const auto dev = xq.device();
+  check_mx_u8(fn, "x codes", xq, dev, M * K, "M*K");
+  TORCH_CHECK(xs.device() == dev, fn, ": x absmax must be on xq's device");
+  TORCH_CHECK(xs.scalar_type() == torch::kFloat32, fn, ": x absmax must be fp32");
+  TORCH_CHECK(xs.is_contiguous(), fn, ": x absmax must be contiguous");
+  TORCH_CHECK(xs.numel() == M, fn, ": x absmax must hold one value per row");
+  check_mx_u8(fn, "w codes", wq, dev, N * K / 2, "N*K/2");
+  check_mx_u8(fn, "w scales", wscales, dev, N * K / MX_BLOCK, "N*K/32");
+  int r = 0;
+  torch::Tensor t_scaled;
+  if (t.defined() && t.numel() > 0) {
+    check_mx_bf16(fn, "t", t, dev);
+    TORCH_CHECK(t.dim() == 2 && t.size(0) == M, fn, ": t must be [M, r]");
+    r = (int)t.size(1);
+    TORCH_CHECK(t.size(1) % 64 == 0 && t.size(1) <= 256, fn,
+                ": r must be a multiple of 64, <= 256");
+    TORCH_CHECK(bw.defined(), fn, ": bw is required with t");
+    check_mx_bf16(fn, "bw", bw, dev);
+    TORCH_CHECK(bw.dim() == 2 && bw.size(0) == N && bw.size(1) == r, fn,
+                ": bw must be [N, r]");
+    // fold the LoRA scale into t, as the other fused GEMMs do
+    t_scaled = (lora_scale == 1.0) ? t : (t * lora_scale).contiguous();
+  }
+  const __hip_bfloat16* bias_p = nullptr;
+  if (bias.defined() && bias.numel() > 0) {
+    check_mx_bf16(fn, "bias", bias, dev);
+    TORCH_CHECK(bias.numel() == N, fn, ": bias must have N elements");
+    bias_p = (const __hip_bfloat16*)bias.data_ptr();
+  }
+  auto y = torch::empty({M, N}, xq.options().dtype(torch::kBFloat16));
+  auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
+  dim3 grid((unsigned)((M >> 8) * (N >> 8))), block(512);
+  hipLaunchKernelGGL(fused_mxfp4_gemm_kernel, grid, block, MX_SMEM_BYTES, stream,
+                     xq.data_ptr<uint8_t>(), xs.data_ptr<float>(), wq.data_ptr<uint8_t>(),
+                     (const unsigned*)wscales.data_ptr<uint8_t>(),
+                     r > 0 ? (const __hip_bfloat16*)t_scaled.data_ptr() : nullptr,
+                     r > 0 ? (const __hip_bfloat16*)bw.data_ptr() : nullptr, bias_p,
+                     (__hip_bfloat16*)y.data_ptr(), M, N, K, r);
+  HIP_CHECK_LAST();
+  return y;
+}
+
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma clang attribute pop
+#endif

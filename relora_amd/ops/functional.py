@@ -801,9 +801,9 @@ class _FusedLoRALinear(torch.autograd.Function):
 
 
 class _QuantizedLoRALinear(torch.autograd.Function):
-    """K15 path: frozen W stays NF4/int8/fp8-packed end to end.  Forward runs
-    the dequant-fused MFMA GEMM (aligned NF4/int8 shapes), the fp8-code GEMM
-    on per-row quantised activations (aligned fp8 shapes) or a transient
+    """K15 path: frozen W stays NF4/int8/fp8/MXFP4-packed end to end.  Forward
+    runs the dequant-fused MFMA GEMM (aligned NF4/int8 shapes), the fp8- or
+    MXFP4-code GEMM on per-row quantised activations (aligned shapes) or a transient
     materialize; backward re-dequantizes transiently for dX.  Unlike the
     dense path, NO dense [N,K] W is ever saved for backward — the HBM
     footprint of the frozen weights stays at the packed size (the entire
@@ -837,6 +837,16 @@ class _QuantizedLoRALinear(torch.autograd.Function):
             # the unaligned arm below multiplies bf16 activations instead
             xq, xs = hip.ext().quantize_rows_fp8(x2d)
             y = hip.ext().fused_fp8_gemm(
+                xq, xs, qw.qdata, qw.absmax, N, t_u, lora_B,
+                bias if bias is not None else empty, scale)
+            del xq, xs
+        elif aligned and qw.mode == "mxfp4" and K % 128 == 0 and K <= 8192:
+            # the same e4m3 activations against the MXFP4 codes as stored.
+            # K > 8192 stays on the materialize arm: the activation quantiser
+            # loops there and the pair measured 1.2 % slower than that arm at
+            # (16384, 4096, 11008) (profiles/stage15_mxfp4_gemm.md)
+            xq, xs = hip.ext().quantize_rows_fp8(x2d)
+            y = hip.ext().fused_mxfp4_gemm(
                 xq, xs, qw.qdata, qw.absmax, N, t_u, lora_B,
                 bias if bias is not None else empty, scale)
             del xq, xs

@@ -1,4 +1,4 @@
-"""Frozen-weight quantization (K15): blockwise NF4 and int8, row-wise fp8.
+"""Frozen-weight quantization (K15): blockwise NF4 and int8, row-wise fp8, MXFP4.
 
 MI355X-native replacement for the reference's bitsandbytes usage
 (reference relora.py:225-238, 277-299): the frozen `W` of a wrapped Linear
@@ -11,6 +11,12 @@ dequant -> W += s·BA -> requant (the reference's exact flow).
 shapes its forward GEMM runs on the codes themselves (f8f6f4 matrix
 instructions, relora_amd/ops/csrc/fp8_gemm.hip) with the activations
 quantised per token row.
+
+`mxfp4` stores OCP MX blocks along K: e2m1 codes, two a byte, and one E8M0
+scale byte per 32 elements (4.25 bits per weight).  On aligned shapes the
+forward multiplies the e4m3 activations of the fp8 mode with the codes as
+stored, on the block-scaled matrix instructions
+(relora_amd/ops/csrc/mxfp4_gemm.hip).
 
 GPU path: relora_amd/ops/csrc/quantize.hip.  The pure-python reference
 implementations here are the CPU path and the kernels' numerics oracle.
@@ -103,8 +109,57 @@ def dequantize_fp8_ref(codes, absmax, dtype=torch.float32):
     return v.to(dtype)
 
 
+MX_BLOCK = 32
+E2M1_VALUES = torch.tensor([0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0])
+
+
+def quantize_mxfp4_ref(w):
+    """python oracle and definition of the format: w [N, K] ->
+    (codes uint8 [N, Kp/2], scales uint8 [N, Kp/32]), Kp = K rounded up to 32.
+
+    A block is 32 consecutive k of one row; a short last block is padded with
+    zeros, which encode as zero codes.  Scale byte (E8M0, value 2^(byte-127)):
+    clamp(E - 2, 0, 254) with E the biased exponent field of the block's fp32
+    amax, 127 for an all-zero block.  Code: e2m1 of v * 2^(127-byte) (exact in
+    fp32), magnitude rounded to nearest with ties to the even code and
+    saturating at 6, sign in bit 3.  The sign bit of v is always kept, so -0
+    and values that round to zero encode as code 8 (they decode to -0).
+    Packing: the low nibble of a byte is the lower k."""
+    v = w.detach().float()
+    N, K = v.shape
+    nb = (K + MX_BLOCK - 1) // MX_BLOCK
+    padded = torch.zeros(N, nb * MX_BLOCK, dtype=torch.float32)
+    padded[:, :K] = v
+    blocks = padded.view(N, nb, MX_BLOCK)
+    amax = blocks.abs().amax(dim=2)
+    e = (amax.view(torch.int32) >> 23) & 0xFF
+    byte = torch.where(amax > 0, (e - 2).clamp(0, 254), torch.full_like(e, 127))
+    inv = ((254 - byte) << 23).view(torch.float32)      # 2^(127-byte), a normal fp32
+    s = blocks * inv.unsqueeze(2)
+    a = s.abs()
+    mag = ((a > 0.25).int() + (a >= 0.75) + (a > 1.25) + (a >= 1.75) + (a > 2.5)
+           + (a >= 3.5) + (a > 5.0))
+    code = (mag | ((s.view(torch.int32) >> 28) & 8)).view(N, nb * MX_BLOCK // 2, 2)
+    codes = (code[..., 0] | (code[..., 1] << 4)).to(torch.uint8)
+    return codes.contiguous(), byte.to(torch.uint8)
+
+
+def dequantize_mxfp4_ref(codes, scales, K, dtype=torch.float32):
+    """value = e2m1(code) * 2^(byte-127), exact in fp32 and bf16; the padding
+    of a short last block is cut off."""
+    N = codes.shape[0]
+    c = torch.stack((codes & 0xF, codes >> 4), dim=2).view(N, -1).long()
+    mag = E2M1_VALUES[c & 7]
+    val = torch.where((c & 8) != 0, -mag, mag)
+    b = scales.to(torch.int32)
+    sc = torch.where(b > 0, b << 23, torch.full_like(b, 0x00400000)).view(torch.float32)
+    out = val.view(N, -1, MX_BLOCK) * sc.unsqueeze(2)
+    return out.view(N, -1)[:, :K].to(dtype)
+
+
 class QuantizedWeight(nn.Module):
-    """A frozen 2-D weight stored quantized (blockwise NF4/int8, row-wise fp8).
+    """A frozen 2-D weight stored quantized (blockwise NF4/int8, row-wise fp8,
+    MXFP4 blocks along K).
 
     Quantization happens on first materialization on a CUDA device (CPU
     keeps the python reference path for tests).  `materialize()` returns a
@@ -114,7 +169,7 @@ class QuantizedWeight(nn.Module):
 
     def __init__(self, weight, mode):
         super().__init__()
-        if mode not in ("4bit", "8bit", "fp8"):
+        if mode not in ("4bit", "8bit", "fp8", "mxfp4"):
             raise ValueError(f"unknown quantize mode {mode!r}")
         self.mode = mode
         self.out_features, self.in_features = weight.shape
@@ -131,6 +186,13 @@ class QuantizedWeight(nn.Module):
             else:
                 q, absmax = quantize_fp8_ref(w)
             q = q.view(-1)
+        elif self.mode == "mxfp4":
+            # qdata: codes uint8 [N, Kp/2]; absmax: the uint8 E8M0 block
+            # scales [N, Kp/32] under the buffer name of the other modes
+            if w.is_cuda:
+                q, absmax = hip.ext().quantize_rows_mxfp4(w.contiguous().to(torch.bfloat16))
+            else:
+                q, absmax = quantize_mxfp4_ref(w)
         elif w.is_cuda:
             wc = w.contiguous().to(torch.bfloat16)
             if self.mode == "4bit":
@@ -154,6 +216,13 @@ class QuantizedWeight(nn.Module):
                 flat = hip.ext().dequantize_rows_fp8(self.qdata, self.absmax, N, K, tdtype)
             else:
                 flat = dequantize_fp8_ref(self.qdata.view(N, K), self.absmax, dtype)
+        elif self.mode == "mxfp4":
+            N, K = self.out_features, self.in_features
+            if self.qdata.is_cuda:
+                tdtype = torch.bfloat16 if dtype in (torch.bfloat16, torch.float16) else torch.float32
+                flat = hip.ext().dequantize_rows_mxfp4(self.qdata, self.absmax, N, K, tdtype)
+            else:
+                flat = dequantize_mxfp4_ref(self.qdata, self.absmax, K, dtype)
         elif self.qdata.is_cuda:
             tdtype = torch.bfloat16 if dtype in (torch.bfloat16, torch.float16) else torch.float32
             if self.mode == "4bit":
@@ -178,11 +247,11 @@ class QuantizedWeight(nn.Module):
 
 
 # absmax must survive model-wide dtype casts (a .to(bf16) on the model would
-# otherwise downcast the fp32 scales)
+# otherwise downcast the fp32 scales); mxfp4's are uint8 bytes and stay so
 def _quantized_apply(self, fn, recurse=True):
     before = self.absmax
     out = nn.Module._apply(self, fn, recurse)
-    if self.absmax.dtype != torch.float32:
+    if self.mode != "mxfp4" and self.absmax.dtype != torch.float32:
         if self.mode == "fp8":
             # a row scale rounded to bf16 would move the whole row: put the
             # fp32 values back instead of widening the rounded ones

@@ -18,7 +18,11 @@ MI355X notes:
   ops/csrc/quantize.hip): W lives quantized at rest, dequantizes per GEMM,
   and the merge runs dequant -> += BA·s -> requant;
 * `quantize="fp8"` stores e4m3 codes with one scale per output row and, on
-  aligned shapes, multiplies on the codes directly (ops/csrc/fp8_gemm.hip).
+  aligned shapes, multiplies on the codes directly (ops/csrc/fp8_gemm.hip);
+* `quantize="mxfp4"` stores OCP MXFP4 blocks (e2m1 codes, one E8M0 scale per
+  32 elements of a row) and, on aligned shapes, multiplies e4m3 activations
+  with the stored codes on the block-scaled matrix instructions
+  (ops/csrc/mxfp4_gemm.hip).
 """
 
 import json
@@ -226,9 +230,9 @@ class ReLoRaLinear(nn.Module):
         super().__init__()
         if r <= 0:
             raise ValueError("LoRA rank r must be >= 1; for a rank-0 (plain) layer just skip the ReLoRA wrap.")
-        if quantize not in (None, "4bit", "8bit", "fp8"):
+        if quantize not in (None, "4bit", "8bit", "fp8", "mxfp4"):
             raise ValueError(
-                f"quantize must be None, '4bit', '8bit' or 'fp8', got {quantize!r}")
+                f"quantize must be None, '4bit', '8bit', 'fp8' or 'mxfp4', got {quantize!r}")
 
         if lora_only:
             self.weight = None

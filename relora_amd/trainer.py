@@ -154,7 +154,7 @@ def parse_args(args=None):
                         default="bfloat16" if torch.cuda.is_available() else "float32")
     parser.add_argument("--workers", type=int, default=8)
 
-    parser.add_argument("--quantize", default=None, type=str, choices=[None, "4bit", "8bit", "fp8"])
+    parser.add_argument("--quantize", default=None, type=str, choices=[None, "4bit", "8bit", "fp8", "mxfp4"])
     parser.add_argument("--use_double_quant", default=True, type=lambda x: x.lower() == "true")
 
     parser.add_argument("--distributed_type", type=str, default="ddp", choices=["fsdp", "ddp"])

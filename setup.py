@@ -43,6 +43,7 @@ ext = CUDAExtension(
         os.path.join(CSRC, "fused_gemm.hip"),
         os.path.join(CSRC, "quantize.hip"),
         os.path.join(CSRC, "fp8_gemm.hip"),
+        os.path.join(CSRC, "mxfp4_gemm.hip"),
     ],
     extra_compile_args={
         "cxx": ["-O3", "-std=c++17"],

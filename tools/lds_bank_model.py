@@ -247,6 +247,9 @@ if __name__ == "__main__":
     import lds_bank_model as _self  # the fp8 patterns are defined further down
     f8_ok, f8_w = verify(_self.fp8_gemm_frag_reads(), "read_b128")
     print(f"fp8_gemm fragment reads: {'conflict-free' if f8_ok else f'{f8_w}-way'}")
+    for name, swz in (("swizzled", _self.mxfp4_gemm_swz_b), ("linear", lambda o: o)):
+        b_ok, b_w = verify(_self.mxfp4_gemm_b_frag_reads(swz), "read_b128")
+        print(f"mxfp4_gemm B fragment reads, {name}: {'conflict-free' if b_ok else f'{b_w}-way'}")
 
 
 # ---------------------------------------------------------------------------
@@ -361,3 +364,21 @@ def fp8_gemm_stage_sources(piece):
     """glds staging of one 1-KiB piece: LDS byte (lane-linear) -> source byte
     of the tile; must be a permutation of the piece's own 8 rows."""
     return [fp8_gemm_swz(piece * 1024 + lane * 16) for lane in range(64)]
+
+
+# ---------------------------------------------------------------------------
+# mxfp4_gemm.hip.  The A (e4m3) image and the bf16 LoRA images are fp8_gemm's
+# ([256][128 B], fp8_gemm_swz, chunks fq and 4+fq: fp8_gemm_frag_reads).  The
+# B (e2m1) image is [256][64 B]: lane (fr, fq) reads chunk fq of row fr with
+# one b128 read.  Linear is 2-way (rows 0-3 and 12-15 of a service group share
+# bank slots); chunk ^= 2*row[3] is conflict-free.
+# ---------------------------------------------------------------------------
+
+def mxfp4_gemm_swz_b(o):
+    return o ^ (((o >> 9) & 1) << 5)
+
+
+def mxfp4_gemm_b_frag_reads(swz=mxfp4_gemm_swz_b, row0s=range(0, 256, 16)):
+    """the one b128 read of an e2m1 fragment: chunk fq of a 64-byte row."""
+    for row0 in row0s:
+        yield {l: swz((row0 + (l & 15)) * 64 + (l >> 4) * 16) for l in range(64)}
