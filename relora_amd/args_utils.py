@@ -138,6 +138,13 @@ def check_args_torchrun_main(args, n_cli_args=None):
     if not -(1 << 63) <= args.adam_rounding_seed < (1 << 63):
         raise ValueError("--adam_rounding_seed must fit in 64 bits")
 
+    fp8_bwd = getattr(args, "fp8_backward", False)
+    if isinstance(fp8_bwd, str):  # YAML
+        fp8_bwd = fp8_bwd.lower() == "true"
+    args.fp8_backward = bool(fp8_bwd)
+    if args.fp8_backward and getattr(args, "quantize", None) != "fp8":
+        raise ValueError("--fp8_backward true needs --quantize fp8")
+
     if getattr(args, "intra_doc_masking", False) and _is_pythia_run(args):
         raise ValueError(
             "--intra_doc_masking is implemented for the LLaMA models only; "

@@ -117,6 +117,8 @@ torch::Tensor dequantize_rows_fp8(torch::Tensor q, torch::Tensor absmax, long R,
 torch::Tensor fused_fp8_gemm(torch::Tensor xq, torch::Tensor xs, torch::Tensor wq,
                              torch::Tensor ws, long N, torch::Tensor t, torch::Tensor bw,
                              torch::Tensor bias, double lora_scale);
+std::vector<torch::Tensor> quantize_rows_fp8_scaled(torch::Tensor dy, torch::Tensor ws);
+torch::Tensor fused_fp8_gemm_dx(torch::Tensor gq, torch::Tensor gs, torch::Tensor wq, long K);
 // mxfp4_gemm.hip
 std::vector<torch::Tensor> quantize_rows_mxfp4(torch::Tensor x);
 torch::Tensor dequantize_rows_mxfp4(torch::Tensor codes, torch::Tensor scales, long R, long K,
@@ -226,6 +228,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "y = (xq@wq^T)*sx*sw^T (+bias) + s*t@Bw^T on the f8f6f4 MFMA, 256^2 glds tile (gfx950)",
         py::arg("xq"), py::arg("xs"), py::arg("wq"), py::arg("ws"), py::arg("N"),
         py::arg("t"), py::arg("bw"), py::arg("bias"), py::arg("lora_scale"));
+  // ws: the absmax of W's rows; g = dy * (ws/448) gets the row rule of quantize_rows_fp8
+  m.def("quantize_rows_fp8_scaled", &quantize_rows_fp8_scaled,
+        "bf16 dy [M,N], fp32 ws [N] -> (e4m3 codes of dy*diag(ws/448) uint8 [M,N], fp32 absmax "
+        "[M]) (gfx950)",
+        py::arg("dy"), py::arg("ws"));
+  // gq / gs: quantize_rows_fp8_scaled of the gradient; wq: the [N,K] codes of W as stored
+  m.def("fused_fp8_gemm_dx", &fused_fp8_gemm_dx,
+        "dx = (gq@wq)*sg on the f8f6f4 MFMA, W transposed in registers on the way to LDS, "
+        "256^2 tile (gfx950)",
+        py::arg("gq"), py::arg("gs"), py::arg("wq"), py::arg("K"));
   m.def("quantize_rows_mxfp4", &quantize_rows_mxfp4,
         "bf16 [R,K] -> (e2m1 codes uint8 [R,Kp/2], E8M0 scales uint8 [R,Kp/32]), OCP MX "
         "blocks of 32 along K (gfx950)");

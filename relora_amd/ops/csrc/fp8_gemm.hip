@@ -533,6 +533,351 @@ torch::Tensor fused_fp8_gemm(torch::Tensor xq, torch::Tensor xs, torch::Tensor w
   return y;
 }
 
+
+// ===========================================================================
+// fp8 backward (`--fp8_backward`): dx = dy @ W on the e4m3 codes of W as
+// stored.  dx[m,k] = sum_n dy[m,n] * code_w[n,k] * sw[n] reduces over W's
+// rows, so W's row scale varies along the reduction.  It is folded into the
+// gradient BEFORE that is quantised — g = dy * diag(sw) — and g gets the
+// ordinary per-token-row e4m3 quantisation; the GEMM then runs on raw codes
+// of both operands with one rank-1 scale (g's) in the epilogue.
+//
+//   quantize_rows_fp8_scaled  bf16 dy [M,N], fp32 ws [N] -> (codes, absmax)
+//   fused_fp8_gemm_dx         dx = (gq · wq) · sg, bf16 out [M,K]
+// ===========================================================================
+
+struct Unit16f { float v[16]; };
+
+// g = float(dy) * (ws/448): the quotient as fused_fp8_gemm_kernel spells sw,
+// the product rounded once to fp32.  `ws16` is the unit's 64 bytes of ws.
+DEV_INLINE Unit16f unit_scale(const Unit16& u, const float* __restrict__ ws16) {
+  const unsigned w[8] = {u.lo.x, u.lo.y, u.lo.z, u.lo.w, u.hi.x, u.hi.y, u.hi.z, u.hi.w};
+  Unit16f g;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const float4 s = reinterpret_cast<const float4*>(ws16)[i];
+    g.v[4 * i + 0] = __fmul_rn(__uint_as_float(w[2 * i] << 16), __fdiv_rn(s.x, FP8_MAX));
+    g.v[4 * i + 1] = __fmul_rn(__uint_as_float(w[2 * i] & 0xffff0000u), __fdiv_rn(s.y, FP8_MAX));
+    g.v[4 * i + 2] = __fmul_rn(__uint_as_float(w[2 * i + 1] << 16), __fdiv_rn(s.z, FP8_MAX));
+    g.v[4 * i + 3] =
+        __fmul_rn(__uint_as_float(w[2 * i + 1] & 0xffff0000u), __fdiv_rn(s.w, FP8_MAX));
+  }
+  return g;
+}
+
+DEV_INLINE float unitf_absmax(const Unit16f& g) {
+  float am = 0.f;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) am = fmaxf(am, fabsf(g.v[i]));
+  return am;
+}
+
+DEV_INLINE uint4 unitf_encode(const Unit16f& g, float inv) {
+  unsigned o[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    int p = __builtin_amdgcn_cvt_pk_fp8_f32(__fmul_rn(g.v[4 * i], inv),
+                                            __fmul_rn(g.v[4 * i + 1], inv), 0, false);
+    p = __builtin_amdgcn_cvt_pk_fp8_f32(__fmul_rn(g.v[4 * i + 2], inv),
+                                        __fmul_rn(g.v[4 * i + 3], inv), p, true);
+    o[i] = (unsigned)p;
+  }
+  return make_uint4(o[0], o[1], o[2], o[3]);
+}
+
+// Geometry of quantize_rows_fp8_kernel; the scaled fp32 units (16 VGPRs each)
+// stay in registers between the max reduction and the conversion.  NU == 0
+// loops (N > 8192) and rebuilds g from L2 in the second pass.
+template <int G, int NU>
+__global__ __launch_bounds__(256) void quantize_rows_fp8_scaled_kernel(
+    const __hip_bfloat16* __restrict__ x, const float* __restrict__ ws,
+    uint8_t* __restrict__ q, float* __restrict__ absmax, long R, int N) {
+  const int gl = threadIdx.x & (G - 1);
+  const long row = ((long)blockIdx.x * 256 + threadIdx.x) / G;
+  const bool live = row < R;  // whole lane groups: shuffles stay inside a row
+  const int units = N >> 4;
+  const Unit16* src = reinterpret_cast<const Unit16*>(x + (live ? row : 0) * N);
+  uint4* dst = reinterpret_cast<uint4*>(q + (live ? row : 0) * N);
+  float am = 0.f;
+  if (NU > 0) {
+    Unit16f g[NU > 0 ? NU : 1];
+#pragma unroll
+    for (int i = 0; i < NU; ++i) {
+      const int c = gl + i * G;
+      if (live && c < units) {
+        g[i] = unit_scale(src[c], ws + c * 16);
+      } else {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) g[i].v[e] = 0.f;
+      }
+      am = fmaxf(am, unitf_absmax(g[i]));
+    }
+    am = group_max<G>(am);
+    const float inv = am > 0.f ? __fdiv_rn(FP8_MAX, am) : 0.f;
+#pragma unroll
+    for (int i = 0; i < NU; ++i) {
+      const int c = gl + i * G;
+      if (live && c < units) dst[c] = unitf_encode(g[i], inv);
+    }
+  } else {
+    if (live)
+      for (int c = gl; c < units; c += G)
+        am = fmaxf(am, unitf_absmax(unit_scale(src[c], ws + c * 16)));
+    am = group_max<G>(am);
+    const float inv = am > 0.f ? __fdiv_rn(FP8_MAX, am) : 0.f;
+    if (live)
+      for (int c = gl; c < units; c += G)
+        dst[c] = unitf_encode(unit_scale(src[c], ws + c * 16), inv);
+  }
+  if (live && gl == 0) absmax[row] = am;
+}
+
+template <int G, int NU>
+static void launch_quantize_scaled(const torch::Tensor& x, const torch::Tensor& ws,
+                                   torch::Tensor& q, torch::Tensor& am, long R, int N,
+                                   hipStream_t stream) {
+  const long rows_per_block = 256 / G;
+  dim3 grid((unsigned)((R + rows_per_block - 1) / rows_per_block)), block(256);
+  hipLaunchKernelGGL((quantize_rows_fp8_scaled_kernel<G, NU>), grid, block, 0, stream,
+                     (const __hip_bfloat16*)x.data_ptr(), ws.data_ptr<float>(),
+                     q.data_ptr<uint8_t>(), am.data_ptr<float>(), R, N);
+}
+
+// dy [M,N] bf16, ws [N] = the absmax of W's rows as QuantizedWeight keeps them
+std::vector<torch::Tensor> quantize_rows_fp8_scaled(torch::Tensor dy, torch::Tensor ws) {
+  const char* fn = "quantize_rows_fp8_scaled";
+  TORCH_CHECK(dy.is_cuda(), fn, ": dy must be a GPU tensor");
+  TORCH_CHECK(dy.dim() == 2, fn, ": dy must be 2-D [M, N]");
+  TORCH_CHECK(dy.is_contiguous(), fn, ": dy must be contiguous");
+  TORCH_CHECK(dy.scalar_type() == torch::kBFloat16, fn, ": dy must be bf16");
+  const long R = dy.size(0), N = dy.size(1);
+  TORCH_CHECK(R > 0 && N > 0, fn, ": M and N must be > 0");
+  TORCH_CHECK(N % 16 == 0, fn, ": N must be a multiple of 16");
+  TORCH_CHECK(N < (1L << 31) && R < (1L << 31) * 4, fn, ": shape too large");
+  TORCH_CHECK(ws.device() == dy.device(), fn, ": ws must be on dy's device");
+  TORCH_CHECK(ws.scalar_type() == torch::kFloat32, fn, ": ws must be fp32");
+  TORCH_CHECK(ws.is_contiguous(), fn, ": ws must be contiguous");
+  TORCH_CHECK(ws.numel() == N, fn, ": ws must hold one value per column of dy");
+  auto q = torch::empty({R, N}, dy.options().dtype(torch::kUInt8));
+  auto am = torch::empty({R}, dy.options().dtype(torch::kFloat32));
+  auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
+  const int n = (int)N;
+  if (N <= 256) {
+    launch_quantize_scaled<16, 1>(dy, ws, q, am, R, n, stream);
+  } else if (N <= 1024) {
+    launch_quantize_scaled<64, 1>(dy, ws, q, am, R, n, stream);
+  } else if (N <= 2048) {
+    launch_quantize_scaled<64, 2>(dy, ws, q, am, R, n, stream);
+  } else if (N <= 4096) {
+    launch_quantize_scaled<64, 4>(dy, ws, q, am, R, n, stream);
+  } else if (N <= 8192) {
+    launch_quantize_scaled<64, 8>(dy, ws, q, am, R, n, stream);
+  } else {
+    launch_quantize_scaled<64, 0>(dy, ws, q, am, R, n, stream);
+  }
+  HIP_CHECK_LAST();
+  return {q, am};
+}
+
+// ---------------------------------------------------------------------------
+// fused_fp8_gemm_dx.  Geometry of fused_fp8_gemm_kernel (256x256 tile over
+// [M,K], 8 waves 2x4, 128-deep reduction tiles over n, double buffer, one
+// vmcnt(0) + barrier per tile, XCD remap, 16x16x128 MFMA, staged b128 store).
+// A = gq [M,N] is reduction-contiguous: glds staging and frag_fp8 as above.
+//
+// B = W [N,K] arrives transposed: a reduction tile is [128 n][256 k] bytes
+// and a fragment wants 32 bytes along n.  Each thread owns one 16 n x 4 k
+// patch: 16 dword loads issued one tile ahead (they fly during the MFMAs),
+// a byte transposition of the four 4x4 blocks with v_perm_b32, and four
+// b128 stores into a [256 k][128 n] image with the swz8 swizzle, which
+// frag_fp8 then reads unchanged.
+//
+// Patch assignment (wave w, lane l):  k-quad q = l[1:0] | l[5:3]<<2 | w[0]<<5
+// (image rows 4q..4q+3), n-chunk c = 2*w[2:1] + l[2].  An 8-lane b128 write
+// group then holds 4 values of (row>>1)&7 — all of one parity — times both
+// parities of c: the 8 swizzled chunks are distinct, i.e. conflict-free
+// (tools/lds_bank_model.py fp8_dx_patch_writes; lane l -> rows 4l..4l+3 is
+// 2-way).  A wave's dword load covers 2 rows x 128 contiguous bytes.
+// ---------------------------------------------------------------------------
+
+// bytes {S0 (4..7), S1 (0..3)} picked by the selector's four bytes
+DEV_INLINE unsigned perm_b32(unsigned hi, unsigned lo, unsigned sel) {
+  return __builtin_amdgcn_perm(hi, lo, sel);
+}
+
+// issue the 16 dword loads of this thread's patch of one W reduction tile;
+// `tile` points at W[n_tile0][k0] (uniform), `voff` is the lane's byte offset
+DEV_INLINE void load_b_patch(unsigned (&st)[16], const char* tile, long K, unsigned voff) {
+#pragma unroll
+  for (int i = 0; i < 16; ++i)
+    st[i] = *reinterpret_cast<const unsigned*>(tile + (long)i * K + voff);
+}
+
+// st[i] holds W[n = 16c + i][k = 4q .. 4q+3]; write image rows 4q..4q+3,
+// 16-byte chunk c (n = 16c .. 16c+15 ascending)
+DEV_INLINE void write_b_patch(char* image, const unsigned (&st)[16], int pq, int pc) {
+  unsigned o[4][4];
+#pragma unroll
+  for (int b = 0; b < 4; ++b) {
+    const unsigned lo01 = perm_b32(st[4 * b + 1], st[4 * b + 0], 0x05010400u);
+    const unsigned hi01 = perm_b32(st[4 * b + 1], st[4 * b + 0], 0x07030602u);
+    const unsigned lo23 = perm_b32(st[4 * b + 3], st[4 * b + 2], 0x05010400u);
+    const unsigned hi23 = perm_b32(st[4 * b + 3], st[4 * b + 2], 0x07030602u);
+    o[0][b] = perm_b32(lo23, lo01, 0x05040100u);
+    o[1][b] = perm_b32(lo23, lo01, 0x07060302u);
+    o[2][b] = perm_b32(hi23, hi01, 0x05040100u);
+    o[3][b] = perm_b32(hi23, hi01, 0x07060302u);
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const unsigned p = swz8((unsigned)(4 * pq + j) * 128u + (unsigned)pc * 16u);
+    *reinterpret_cast<i32x4_q*>(image + p) =
+        i32x4_q{(int)o[j][0], (int)o[j][1], (int)o[j][2], (int)o[j][3]};
+  }
+}
+
+__global__ __launch_bounds__(512) void fused_fp8_gemm_dx_kernel(
+    const uint8_t* __restrict__ gq,    // [M,N] e4m3 codes of dy*diag(sw)
+    const float* __restrict__ ga,      // [M] absmax of its rows
+    const uint8_t* __restrict__ wq,    // [N,K] e4m3 codes of W
+    __hip_bfloat16* __restrict__ dx,   // [M,K]
+    long M, long N, long K) {
+  // one __shared__ array only (glds pipeline rule)
+  extern __shared__ __attribute__((aligned(16))) char smem[];  // [2][A | B] = 128 KiB
+
+  // XCD-aware blockIdx remap (bijective form), as in fused_fp8_gemm_kernel
+  const int nwg = gridDim.x;
+  const int q8 = nwg >> 3, r8 = nwg & 7;
+  int wgid = blockIdx.x;
+  if (nwg >= 8) {
+    const int xcd = wgid & 7, pos = wgid >> 3;
+    wgid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + pos;
+  }
+  const int nbk = (int)(K >> 8);
+  const long m0 = (long)(wgid / nbk) << 8;
+  const long k0 = (long)(wgid % nbk) << 8;
+
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int wr = wave >> 2;   // 0..1: wave m-position (128 rows)
+  const int wc = wave & 3;    // 0..3: wave k-position (64 cols)
+  const int fr = lane & 15;   // fragment row / C column
+  const int fq = lane >> 4;   // fragment n-group / C row group
+
+  // this thread's patch of every W tile
+  const int pq = (lane & 3) | ((lane >> 3) << 2) | ((wave & 1) << 5);
+  const int pc = (wave >> 1) * 2 + ((lane >> 2) & 1);
+  const unsigned voff = (unsigned)(pc * 16) * (unsigned)K + (unsigned)(pq * 4);
+
+  f32x4_q acc[8][4];
+#pragma unroll
+  for (int i = 0; i < 8; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_q{0.f, 0.f, 0.f, 0.f};
+
+  const char* gg = (const char*)gq;
+  const char* wg = (const char*)wq + k0;
+  unsigned st[16];
+
+  const int NT = (int)(N >> 7);  // 128-n tiles
+  stage_tile_bytes(FP8_BUF_A(0), gg, m0, N, 0, wave, lane);
+  load_b_patch(st, wg, K, voff);
+  write_b_patch(FP8_BUF_B(0), st, pq, pc);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+
+  for (int nt = 0; nt < NT; ++nt) {
+    const int cur = nt & 1;
+    const bool more = nt + 1 < NT;
+    if (more) {
+      stage_tile_bytes(FP8_BUF_A(cur ^ 1), gg, m0, N, (long)(nt + 1) << 7, wave, lane);
+      // keep the lane offset a 32-bit VGPR next to scalar row bases (saddr
+      // form): hoisted out of the loop it becomes 16 64-bit lane addresses
+      unsigned vo = voff;
+      asm volatile("" : "+v"(vo));
+      load_b_patch(st, wg + ((long)(nt + 1) << 7) * K, K, vo);
+    }
+    const char* A = FP8_BUF_A(cur);
+    const char* B = FP8_BUF_B(cur);
+    __builtin_amdgcn_s_setprio(1);
+    // the 4 B fragments stay resident (32 VGPRs); A fragments stream through
+    i32x8_q bf[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) bf[j] = frag_fp8(B, wc * 64 + j * 16 + fr, fq);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const i32x8_q af = frag_fp8(A, wr * 128 + i * 16 + fr, fq);
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
+            af, bf[j], acc[i][j], 0 /*A e4m3*/, 0 /*B e4m3*/, 0, 0, 0, 0);
+    }
+    __builtin_amdgcn_s_setprio(0);
+    // the other B image was last read in the previous iteration, behind its
+    // barrier; the patch loads had the whole MFMA loop to land
+    if (more) write_b_patch(FP8_BUF_B(cur ^ 1), st, pq, pc);
+    // drain next tile's glds, then release the buffers we just read
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+  }
+
+  // ---- the one rank-1 scale, one bf16 rounding, b128 row stores through LDS
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const f32x4_q ax = *reinterpret_cast<const f32x4_q*>(ga + m0 + wr * 128 + i * 16 + fq * 4);
+    const f32x4_q sg = {__fdiv_rn(ax[0], FP8_MAX), __fdiv_rn(ax[1], FP8_MAX),
+                        __fdiv_rn(ax[2], FP8_MAX), __fdiv_rn(ax[3], FP8_MAX)};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = acc[i][j] * sg;
+  }
+  __bf16* mine = (__bf16*)smem + wave * (128 * 64);  // 16 KiB per wave
+#pragma unroll
+  for (int i = 0; i < 8; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg)
+        mine[(i * 16 + fq * 4 + reg) * 64 + j * 16 + fr] = (__bf16)acc[i][j][reg];
+  // no barrier needed: each wave reads only its own region
+#pragma unroll
+  for (int rr = 0; rr < 16; ++rr) {
+    const int row = rr * 8 + (lane >> 3);          // 0..127
+    const int cb = (lane & 7) * 8;                 // 8-col chunk
+    const bf16x8_q vv = *reinterpret_cast<const bf16x8_q*>(mine + row * 64 + cb);
+    *reinterpret_cast<bf16x8_q*>(dx + (m0 + wr * 128 + row) * K + k0 + wc * 64 + cb) = vv;
+  }
+}
+
+// gq / gs: quantize_rows_fp8_scaled(dy, W's absmax); wq: W's codes [N,K]
+torch::Tensor fused_fp8_gemm_dx(torch::Tensor gq, torch::Tensor gs, torch::Tensor wq, long K) {
+  const char* fn = "fused_fp8_gemm_dx";
+  TORCH_CHECK(gq.is_cuda(), fn, ": gq must be a GPU tensor");
+  TORCH_CHECK(gq.dim() == 2, fn, ": gq must be 2-D [M, N]");
+  const long M = gq.size(0), N = gq.size(1);
+  TORCH_CHECK(M > 0 && N > 0 && K > 0, fn, ": M, N and K must be > 0");
+  TORCH_CHECK(M % 256 == 0 && K % 256 == 0 && N % 128 == 0, fn,
+              " requires M%256==0, K%256==0, N%128==0");
+  TORCH_CHECK(K < (1L << 24) && N < (1L << 31) && (M >> 8) * (K >> 8) < (1L << 31), fn,
+              ": shape too large");
+  const auto dev = gq.device();
+  check_fp8_operand(fn, "g", gq, gs, dev, M, N);
+  TORCH_CHECK(wq.is_cuda() && wq.device() == dev, fn, ": w codes must be on gq's GPU");
+  TORCH_CHECK(wq.scalar_type() == torch::kUInt8, fn, ": w codes must be uint8");
+  TORCH_CHECK(wq.is_contiguous(), fn, ": w codes must be contiguous");
+  TORCH_CHECK(wq.numel() == N * K, fn, ": w codes must hold N*K values");
+  TORCH_CHECK((uintptr_t)gq.data_ptr() % 16 == 0 && (uintptr_t)wq.data_ptr() % 16 == 0, fn,
+              ": code tensors must be 16-byte aligned");
+  auto dx = torch::empty({M, K}, gq.options().dtype(torch::kBFloat16));
+  auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
+  dim3 grid((unsigned)((M >> 8) * (K >> 8))), block(512);
+  const size_t smem = 4 * FP8_TILE_BYTES;  // 128 KiB
+  hipLaunchKernelGGL(fused_fp8_gemm_dx_kernel, grid, block, smem, stream,
+                     gq.data_ptr<uint8_t>(), gs.data_ptr<float>(), wq.data_ptr<uint8_t>(),
+                     (__hip_bfloat16*)dx.data_ptr(), M, N, K);
+  HIP_CHECK_LAST();
+  return dx;
+}
+
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma clang attribute pop
 #endif

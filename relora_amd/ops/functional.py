@@ -811,7 +811,8 @@ class _QuantizedLoRALinear(torch.autograd.Function):
     """
 
     @staticmethod
-    def forward(ctx, x, bias, lora_A, lora_B, scale, dropout_p, training, qw):
+    def forward(ctx, x, bias, lora_A, lora_B, scale, dropout_p, training, qw,
+                fp8_backward=False):
         in_shape = x.shape
         K = in_shape[-1]
         N = qw.out_features
@@ -866,6 +867,7 @@ class _QuantizedLoRALinear(torch.autograd.Function):
         ctx.save_for_backward(x2d, mask if mask is not None else empty,
                               t_u, lora_A, lora_B)
         ctx.qw = qw
+        ctx.fp8_backward = bool(fp8_backward)
         ctx.scale = scale
         ctx.dropout_p = dropout_p if use_dropout else 0.0
         ctx.has_bias = bias is not None
@@ -880,9 +882,18 @@ class _QuantizedLoRALinear(torch.autograd.Function):
         dy2d = dy.contiguous().view(-1, N)
         bs = lora_B * scale
         u_s = dy2d @ bs
-        w = qw.materialize(torch.bfloat16)  # transient dense W for dX only
-        dx = dy2d @ w
-        del w
+        M, K = dy2d.shape[0], qw.in_features
+        if (ctx.fp8_backward and qw.mode == "fp8" and M % 256 == 0 and K % 256 == 0
+                and N % 128 == 0 and _FUSED_K1 != "0"):
+            # opt-in: W's row scales folded into dy, that product quantised per
+            # token row, dx on the e4m3 codes of W as stored (no dense W)
+            gq, gs = hip.ext().quantize_rows_fp8_scaled(dy2d, qw.absmax)
+            dx = hip.ext().fused_fp8_gemm_dx(gq, gs, qw.qdata, K)
+            del gq, gs
+        else:
+            w = qw.materialize(torch.bfloat16)  # transient dense W for dX only
+            dx = dy2d @ w
+            del w
         hip.ext().lora_add_nn_(dx, u_s, lora_A,
                                mask if p > 0 else mask.new_empty(0, dtype=torch.uint8),
                                1.0 / (1.0 - p) if p > 0 else 1.0)
@@ -893,7 +904,7 @@ class _QuantizedLoRALinear(torch.autograd.Function):
         dB = hip.ext().skinny_grad(t_u, dy2d, empty_mask, 1.0, scale, True, lora_B.dtype)
         dbias = dy2d.sum(0) if ctx.has_bias else None
         return (dx.view(dy.shape[:-1] + (qw.in_features,)), dbias,
-                dA, dB, None, None, None, None)
+                dA, dB, None, None, None, None, None)
 
 
 class _HipDropout(torch.autograd.Function):
@@ -937,7 +948,8 @@ def _fused_ok(x, weight, lora_A, scale, lora_only):
 
 
 def lora_linear(x, weight, bias, lora_A, lora_B, scale, dropout_p=0.0,
-                training=False, lora_only=False, quantized_weight=None):
+                training=False, lora_only=False, quantized_weight=None,
+                fp8_backward=False):
     """y = x W^T (+b) + s * dropout(x) A^T B^T.
 
     GPU bf16 path: _FusedLoRALinear (MFMA rank-r accumulate kernels).
@@ -945,13 +957,18 @@ def lora_linear(x, weight, bias, lora_A, lora_B, scale, dropout_p=0.0,
     `scale` may be a python float or a 0-d tensor (trainable scaling,
     already passed through tanh by the caller) — tensor scale uses the
     composed path so autograd reaches it.
+
+    `fp8_backward` (fp8-quantized W on the GPU path only; ignored elsewhere):
+    the input gradient of aligned shapes runs on W's e4m3 codes with the
+    scaled gradient rounded to e4m3 per token row, instead of on a transient
+    bf16 W.
     """
     if quantized_weight is not None:
         if (hip.use_hip(x, "lora") and not lora_only and not torch.is_tensor(scale)
                 and x.dtype == torch.bfloat16):
             return _QuantizedLoRALinear.apply(x, bias, lora_A, lora_B,
                                               float(scale), dropout_p, training,
-                                              quantized_weight)
+                                              quantized_weight, fp8_backward)
         # CPU / tensor-scale fallback: transient materialize + composed ops
         weight = quantized_weight.materialize(x.dtype if x.is_floating_point()
                                               else torch.float32)

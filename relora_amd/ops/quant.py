@@ -88,12 +88,22 @@ def dequantize_int8_ref(q, absmax, n, dtype=torch.float32):
 FP8_MAX = 448.0  # largest finite e4m3fn value
 
 
-def quantize_fp8_ref(x):
+def quantize_fp8_ref(x, col_scale=None):
     """python oracle: x [R, K] -> (e4m3 codes uint8 [R, K], absmax fp32 [R]).
 
     Per row: inv = 448/absmax (one fp32 division), code = e4m3_rne(v*inv)
-    with the product in fp32; a row of zeros gives zero codes."""
+    with the product in fp32; a row of zeros gives zero codes.
+
+    `col_scale` (fp32 [K], the absmax of a row-quantised W whose rows are
+    x's columns): the rule applies to g = x * (col_scale/448) instead, the
+    quotient one fp32 division and the product rounded once to fp32 (the
+    oracle of `quantize_rows_fp8_scaled`, the fp8 backward's quantiser)."""
     v = x.detach().float()
+    if col_scale is not None:
+        cs = col_scale.detach().float()
+        if cs.shape != (v.shape[1],):
+            raise ValueError(f"col_scale must have shape ({v.shape[1]},), got {tuple(cs.shape)}")
+        v = v * (cs / torch.full_like(cs, FP8_MAX)).unsqueeze(0)
     absmax = v.abs().amax(dim=1)
     # a tensor numerator: `448.0 / absmax` would be reciprocal-then-multiply,
     # two roundings where the format asks for one division

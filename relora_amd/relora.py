@@ -176,6 +176,16 @@ class ReLoRaModel(torch.nn.Module):
         self.wrapped_model.set_loss_options(z_loss=z_loss, label_smoothing=label_smoothing)
         return self
 
+    def set_fp8_backward(self, enabled=True):
+        """Runtime switch of every ReLoRaLinear: with `quantize="fp8"` on the
+        GPU, aligned layers compute the input gradient on W's e4m3 codes (the
+        scaled output gradient is rounded to e4m3 per token row).  Not part of
+        relora_config.json; other modes, CPU and unaligned shapes ignore it."""
+        for module in self.modules():
+            if isinstance(module, ReLoRaLinear):
+                module.fp8_backward = bool(enabled)
+        return self
+
     def save_pretrained(self, path):
         # reference layout: pytorch_model.bin (+ config.json) + relora_config.json
         from relora_amd.utils.checkpoint import save_pretrained_compat
@@ -267,6 +277,7 @@ class ReLoRaLinear(nn.Module):
         self.lora_only = lora_only
         self.trainable_scaling = trainable_scaling
         self.quantize = quantize
+        self.fp8_backward = False  # runtime switch, see ReLoRaModel.set_fp8_backward
 
         self.lora_A = nn.Linear(in_features, r, bias=False)
         nn.init.kaiming_uniform_(self.lora_A.weight, a=math.sqrt(5))
@@ -338,6 +349,7 @@ class ReLoRaLinear(nn.Module):
             training=self.training,
             lora_only=self.lora_only,
             quantized_weight=quantized,
+            fp8_backward=self.fp8_backward,
         )
 
     def extra_repr(self):

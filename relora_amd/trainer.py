@@ -156,6 +156,9 @@ def parse_args(args=None):
 
     parser.add_argument("--quantize", default=None, type=str, choices=[None, "4bit", "8bit", "fp8", "mxfp4"])
     parser.add_argument("--use_double_quant", default=True, type=lambda x: x.lower() == "true")
+    parser.add_argument("--fp8_backward", default=False, type=lambda x: x.lower() == "true",
+                        help="with --quantize fp8: input gradients of aligned linears on the "
+                             "fp8 matrix cores (rounds the scaled output gradient to e4m3)")
 
     parser.add_argument("--distributed_type", type=str, default="ddp", choices=["fsdp", "ddp"])
     parser.add_argument("--profile", default=False, type=lambda x: x.lower() == "true")
@@ -600,6 +603,9 @@ def main(args):
             quantize=args.quantize,
             use_double_quant=args.use_double_quant,
         )
+        if args.fp8_backward:
+            model.set_fp8_backward(True)
+            logger.info("fp8 backward: input gradients of aligned fp8 linears on the e4m3 codes")
 
     if args.resume_from:
         logger.info(f"Loading model from {args.resume_from}")

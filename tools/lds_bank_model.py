@@ -382,3 +382,43 @@ def mxfp4_gemm_b_frag_reads(swz=mxfp4_gemm_swz_b, row0s=range(0, 256, 16)):
     """the one b128 read of an e2m1 fragment: chunk fq of a 64-byte row."""
     for row0 in row0s:
         yield {l: swz((row0 + (l & 15)) * 64 + (l >> 4) * 16) for l in range(64)}
+
+
+# ---------------------------------------------------------------------------
+# fused_fp8_gemm_dx (fp8_gemm.hip): the B image is written from registers.  A
+# thread owns a 16 n x 4 k patch of the W tile, transposes it and stores four
+# b128 rows (image rows 4q..4q+3, chunk c) under fp8_gemm_swz; the fragment
+# reads are fp8_gemm_frag_reads unchanged.
+# ---------------------------------------------------------------------------
+
+def fp8_dx_patch(wave, lane):
+    """the kernel's assignment -> (k-quad q, n-chunk c)."""
+    return ((lane & 3) | ((lane >> 3) << 2) | ((wave & 1) << 5),
+            (wave >> 1) * 2 + ((lane >> 2) & 1))
+
+
+def fp8_dx_patch_naive(wave, lane):
+    """lane l -> rows 4l..4l+3, one chunk per wave."""
+    return lane, wave
+
+
+def fp8_dx_patch_writes(assign=fp8_dx_patch):
+    """every b128 write of one B image: (wave, row j of the patch)."""
+    for wave in range(8):
+        for j in range(4):
+            addrs = {}
+            for lane in range(64):
+                q, c = assign(wave, lane)
+                addrs[lane] = fp8_gemm_swz((4 * q + j) * 128 + c * 16)
+            yield addrs
+
+
+def fp8_dx_patch_cover(assign=fp8_dx_patch):
+    """the (q, c) patches of all 512 threads: must be all 64 x 8, once each."""
+    return sorted(assign(w, l) for w in range(8) for l in range(64))
+
+
+if __name__ == "__main__":
+    for name, fn in (("kernel", fp8_dx_patch), ("naive", fp8_dx_patch_naive)):
+        ok, ways = verify(fp8_dx_patch_writes(fn), "write_b128")
+        print(f"fp8_gemm_dx patch writes, {name}: {'conflict-free' if ok else f'{ways}-way'}")
