@@ -3,7 +3,8 @@
 // Reference numerics: fp32 variance, product rounded at bf16
 // (reference modeling_llama.py:74-91).
 //
-// fwd: one block per row, vectorized 8-wide loads, single pass.
+// fwd: one block per row, vectorized 8-wide loads; RMSNorm sums in one pass,
+// LayerNorm in two (mean, then the centred second moment).
 // bwd: dx one block per row; dw/db one thread per column striding rows
 // (coalesced across threads; the re-read of x/dy is HBM-bound and overlaps).
 
@@ -270,26 +271,42 @@ __global__ void layernorm_fwd_kernel(const T* __restrict__ x, const T* __restric
   const T* xr = x + row * (long)H;
   T* yr = y + row * (long)H;
 
-  float s = 0.f, ss = 0.f;
+  // Two passes.  The one-pass var = E[x^2] - mu^2 cancels when the row has a
+  // common offset (|mu| >> std): at mu = 1000, std = 0.01 it is off by more
+  // than var itself.  Pass 1 gives a shift mu0 (the mean up to fp32 summation
+  // error); pass 2 sums d = x - mu0 and d^2 over the row, which pass 1 has
+  // just pulled into cache.  mean(d) corrects the mean, and
+  // var = mean(d^2) - mean(d)^2 holds for any shift and only cancels by the
+  // (tiny) error of mu0.
+  float s = 0.f;
   const int vec_end = (H / 8) * 8;
   for (int i = threadIdx.x * 8; i < vec_end; i += blockDim.x * 8) {
     Vec8<T> v = load8(xr + i);
 #pragma unroll
+    for (int j = 0; j < 8; ++j) s += to_f32(v.v[j]);
+  }
+  for (int i = vec_end + threadIdx.x; i < H; i += blockDim.x) s += to_f32(xr[i]);
+  const float mu0 = block_reduce_sum(s, scratch) / H;
+
+  float sd = 0.f, sdd = 0.f;
+  for (int i = threadIdx.x * 8; i < vec_end; i += blockDim.x * 8) {
+    Vec8<T> v = load8(xr + i);
+#pragma unroll
     for (int j = 0; j < 8; ++j) {
-      float f = to_f32(v.v[j]);
-      s += f;
-      ss += f * f;
+      float d = to_f32(v.v[j]) - mu0;
+      sd += d;
+      sdd += d * d;
     }
   }
   for (int i = vec_end + threadIdx.x; i < H; i += blockDim.x) {
-    float f = to_f32(xr[i]);
-    s += f;
-    ss += f * f;
+    float d = to_f32(xr[i]) - mu0;
+    sd += d;
+    sdd += d * d;
   }
-  s = block_reduce_sum(s, scratch);
-  ss = block_reduce_sum(ss, scratch);
-  const float mu = s / H;
-  const float var = fmaxf(ss / H - mu * mu, 0.f);
+  const float md = block_reduce_sum(sd, scratch) / H;
+  sdd = block_reduce_sum(sdd, scratch);
+  const float mu = mu0 + md;
+  const float var = fmaxf(sdd / H - md * md, 0.f);
   const float istd = rsqrtf(var + eps);
   if (threadIdx.x == 0) {
     mean_out[row] = mu;
@@ -380,12 +397,55 @@ static int norm_block(int H) {
   return 512;
 }
 
+// Host checks, all before any launch.  The kernels take raw pointers, one
+// element type and the lengths of x, so each of these guards a read or a
+// write past an allocation (or a tensor reinterpreted in another type).
+
+// x: the [M, H] activations every other argument is measured against
+static void check_x(const torch::Tensor& x, const char* op) {
+  TORCH_CHECK(x.is_cuda(), op, ": x must be on a GPU");
+  TORCH_CHECK(x.scalar_type() == torch::kBFloat16 || x.scalar_type() == torch::kFloat32,
+              op, ": x must be bf16 or fp32, got ", x.scalar_type());
+  TORCH_CHECK(x.dim() == 2 && x.is_contiguous(), op, ": x must be 2-D and contiguous");
+  TORCH_CHECK(x.size(1) >= 1 && x.size(1) < (1L << 31) && x.size(0) < (1L << 31), op,
+              ": x must have 1 <= H < 2^31 columns and fewer than 2^31 rows");
+}
+
+// w, b: [H] in x's dtype
+static void check_param(const torch::Tensor& p, const torch::Tensor& x, const char* op,
+                        const char* name) {
+  TORCH_CHECK(p.is_cuda() && p.device() == x.device() && p.scalar_type() == x.scalar_type() &&
+                  p.is_contiguous() && p.numel() == x.size(1),
+              op, ": ", name, " must be on x's device, in x's dtype, contiguous, with H = ",
+              x.size(1), " elements");
+}
+
+// res, dy, dsum: everything of x but the values
+static void check_like_x(const torch::Tensor& t, const torch::Tensor& x, const char* op,
+                         const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.device() == x.device() && t.scalar_type() == x.scalar_type() &&
+                  t.sizes() == x.sizes() && t.is_contiguous(),
+              op, ": ", name, " must be on x's device, in x's dtype and shape, contiguous");
+}
+
+// invrms, mean, invstd: fp32 [M]
+static void check_stat(const torch::Tensor& t, const torch::Tensor& x, const char* op,
+                       const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.device() == x.device() &&
+                  t.scalar_type() == torch::kFloat32 && t.is_contiguous() &&
+                  t.numel() == x.size(0),
+              op, ": ", name, " must be on x's device, fp32, contiguous, with M = ", x.size(0),
+              " elements");
+}
+
 std::vector<torch::Tensor> rmsnorm_fwd(torch::Tensor x, torch::Tensor w, double eps) {
-  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.is_contiguous());
+  check_x(x, "rmsnorm_fwd");
+  check_param(w, x, "rmsnorm_fwd", "w");
   const long M = x.size(0);
   const int H = x.size(1);
   auto y = torch::empty_like(x);
   auto invrms = torch::empty({M}, x.options().dtype(torch::kFloat32));
+  if (M == 0) return {y, invrms};
   dim3 grid(M), block(norm_block(H));
   auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
   if (x.scalar_type() == torch::kBFloat16) {
@@ -403,9 +463,14 @@ std::vector<torch::Tensor> rmsnorm_fwd(torch::Tensor x, torch::Tensor w, double 
 
 std::vector<torch::Tensor> rmsnorm_bwd(torch::Tensor x, torch::Tensor w,
                                        torch::Tensor invrms, torch::Tensor dy) {
+  check_x(x, "rmsnorm_bwd");
+  check_param(w, x, "rmsnorm_bwd", "w");
+  check_stat(invrms, x, "rmsnorm_bwd", "invrms");
+  check_like_x(dy, x, "rmsnorm_bwd", "dy");
   const long M = x.size(0);
   const int H = x.size(1);
   auto dx = torch::empty_like(x);
+  if (M == 0) return {dx, torch::zeros({H}, x.options().dtype(torch::kFloat32))};
   auto dw = torch::empty({H}, x.options().dtype(torch::kFloat32));
   auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
   dim3 grid(M), block(norm_block(H));
@@ -438,12 +503,15 @@ std::vector<torch::Tensor> rmsnorm_bwd(torch::Tensor x, torch::Tensor w,
 
 std::vector<torch::Tensor> layernorm_fwd(torch::Tensor x, torch::Tensor w,
                                          torch::Tensor b, double eps) {
-  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.is_contiguous());
+  check_x(x, "layernorm_fwd");
+  check_param(w, x, "layernorm_fwd", "w");
+  check_param(b, x, "layernorm_fwd", "b");
   const long M = x.size(0);
   const int H = x.size(1);
   auto y = torch::empty_like(x);
   auto mean = torch::empty({M}, x.options().dtype(torch::kFloat32));
   auto invstd = torch::empty({M}, x.options().dtype(torch::kFloat32));
+  if (M == 0) return {y, mean, invstd};
   dim3 grid(M), block(norm_block(H));
   auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
   if (x.scalar_type() == torch::kBFloat16) {
@@ -464,9 +532,18 @@ std::vector<torch::Tensor> layernorm_fwd(torch::Tensor x, torch::Tensor w,
 std::vector<torch::Tensor> layernorm_bwd(torch::Tensor x, torch::Tensor w,
                                          torch::Tensor mean, torch::Tensor invstd,
                                          torch::Tensor dy) {
+  check_x(x, "layernorm_bwd");
+  check_param(w, x, "layernorm_bwd", "w");
+  check_stat(mean, x, "layernorm_bwd", "mean");
+  check_stat(invstd, x, "layernorm_bwd", "invstd");
+  check_like_x(dy, x, "layernorm_bwd", "dy");
   const long M = x.size(0);
   const int H = x.size(1);
   auto dx = torch::empty_like(x);
+  if (M == 0) {
+    auto zero = torch::zeros({2, H}, x.options().dtype(torch::kFloat32));
+    return {dx, zero[0], zero[1]};
+  }
   auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
   dim3 grid(M), block(norm_block(H));
   const int nchunks = reduce_chunks(M);
@@ -499,13 +576,15 @@ std::vector<torch::Tensor> layernorm_bwd(torch::Tensor x, torch::Tensor w,
 
 std::vector<torch::Tensor> rmsnorm_fwd_add(torch::Tensor x, torch::Tensor res,
                                            torch::Tensor w, double eps) {
-  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.is_contiguous() && res.is_contiguous());
-  TORCH_CHECK(x.sizes() == res.sizes());
+  check_x(x, "rmsnorm_fwd_add");
+  check_like_x(res, x, "rmsnorm_fwd_add", "res");
+  check_param(w, x, "rmsnorm_fwd_add", "w");
   const long M = x.size(0);
   const int H = x.size(1);
   auto sum_o = torch::empty_like(x);
   auto y = torch::empty_like(x);
   auto invrms = torch::empty({M}, x.options().dtype(torch::kFloat32));
+  if (M == 0) return {y, sum_o, invrms};
   dim3 grid(M), block(norm_block(H));
   auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
   if (x.scalar_type() == torch::kBFloat16) {
@@ -527,11 +606,15 @@ std::vector<torch::Tensor> rmsnorm_bwd_add(torch::Tensor x, torch::Tensor w,
                                            torch::Tensor invrms, torch::Tensor dy,
                                            torch::Tensor dsum) {
   // identical to rmsnorm_bwd but dx += dsum fused; dw reuses the standard path
-  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.is_contiguous());
-  TORCH_CHECK(dy.is_contiguous() && dsum.is_contiguous());
+  check_x(x, "rmsnorm_bwd_add");
+  check_param(w, x, "rmsnorm_bwd_add", "w");
+  check_stat(invrms, x, "rmsnorm_bwd_add", "invrms");
+  check_like_x(dy, x, "rmsnorm_bwd_add", "dy");
+  check_like_x(dsum, x, "rmsnorm_bwd_add", "dsum");
   const long M = x.size(0);
   const int H = x.size(1);
   auto dx = torch::empty_like(x);
+  if (M == 0) return {dx, torch::zeros({H}, x.options().dtype(torch::kFloat32))};
   auto dw = torch::empty({H}, x.options().dtype(torch::kFloat32));
   dim3 grid(M), block(norm_block(H));
   auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();

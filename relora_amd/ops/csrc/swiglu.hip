@@ -120,10 +120,30 @@ static dim3 ew_grid(long n) {
   return dim3(blocks);
 }
 
+// Host checks, all before any launch: the kernels take raw pointers, one
+// element type and g's element count, so each of these guards a read or a
+// write past an allocation (or a tensor reinterpreted in another type).
+static void check_first(const torch::Tensor& g, const char* op, const char* name) {
+  TORCH_CHECK(g.is_cuda(), op, ": ", name, " must be on a GPU");
+  TORCH_CHECK(g.scalar_type() == torch::kBFloat16 || g.scalar_type() == torch::kFloat32,
+              op, ": ", name, " must be bf16 or fp32, got ", g.scalar_type());
+  TORCH_CHECK(g.is_contiguous(), op, ": ", name, " must be contiguous");
+}
+
+static void check_same(const torch::Tensor& t, const torch::Tensor& g, const char* op,
+                       const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.device() == g.device() && t.scalar_type() == g.scalar_type() &&
+                  t.numel() == g.numel() && t.is_contiguous(),
+              op, ": ", name, " must be on the first argument's device, in its dtype, "
+              "contiguous, with as many elements (", g.numel(), ")");
+}
+
 torch::Tensor swiglu_fwd(torch::Tensor g, torch::Tensor u) {
-  TORCH_CHECK(g.is_cuda() && g.is_contiguous() && u.is_contiguous());
+  check_first(g, "swiglu_fwd", "g");
+  check_same(u, g, "swiglu_fwd", "u");
   auto y = torch::empty_like(g);
   long n = g.numel();
+  if (n == 0) return y;
   auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
   if (g.scalar_type() == torch::kBFloat16)
     hipLaunchKernelGGL(swiglu_fwd_kernel<__hip_bfloat16>, ew_grid(n), dim3(256), 0, stream,
@@ -137,9 +157,13 @@ torch::Tensor swiglu_fwd(torch::Tensor g, torch::Tensor u) {
 }
 
 std::vector<torch::Tensor> swiglu_bwd(torch::Tensor g, torch::Tensor u, torch::Tensor dy) {
+  check_first(g, "swiglu_bwd", "g");
+  check_same(u, g, "swiglu_bwd", "u");
+  check_same(dy, g, "swiglu_bwd", "dy");
   auto dg = torch::empty_like(g);
   auto du = torch::empty_like(u);
   long n = g.numel();
+  if (n == 0) return {dg, du};
   auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
   if (g.scalar_type() == torch::kBFloat16)
     hipLaunchKernelGGL(swiglu_bwd_kernel<__hip_bfloat16>, ew_grid(n), dim3(256), 0, stream,
@@ -155,9 +179,10 @@ std::vector<torch::Tensor> swiglu_bwd(torch::Tensor g, torch::Tensor u, torch::T
 }
 
 torch::Tensor gelu_fwd(torch::Tensor x) {
-  TORCH_CHECK(x.is_cuda() && x.is_contiguous());
+  check_first(x, "gelu_fwd", "x");
   auto y = torch::empty_like(x);
   const long n = x.numel();
+  if (n == 0) return y;
   auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
   if (x.scalar_type() == torch::kBFloat16)
     hipLaunchKernelGGL(gelu_fwd_kernel<__hip_bfloat16>, ew_grid(n), dim3(256), 0, stream,
@@ -170,9 +195,11 @@ torch::Tensor gelu_fwd(torch::Tensor x) {
 }
 
 torch::Tensor gelu_bwd(torch::Tensor x, torch::Tensor dy) {
-  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && dy.is_contiguous());
+  check_first(x, "gelu_bwd", "x");
+  check_same(dy, x, "gelu_bwd", "dy");
   auto dx = torch::empty_like(x);
   const long n = x.numel();
+  if (n == 0) return dx;
   auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
   if (x.scalar_type() == torch::kBFloat16)
     hipLaunchKernelGGL(gelu_bwd_kernel<__hip_bfloat16>, ew_grid(n), dim3(256), 0, stream,

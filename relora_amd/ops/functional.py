@@ -45,6 +45,7 @@ class _HipRMSNorm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, eps):
         x2d = x.contiguous().view(-1, x.shape[-1])
+        weight = weight.contiguous()
         y, invrms = hip.ext().rmsnorm_fwd(x2d, weight, eps)
         ctx.save_for_backward(x2d, weight, invrms)
         ctx.shape = x.shape
@@ -58,8 +59,14 @@ class _HipRMSNorm(torch.autograd.Function):
         return dx.view(ctx.shape), dw.to(weight.dtype), None
 
 
+def _same_dtype_device(x, *params):
+    """The norm kernels read weight (and bias) through x's element type; a
+    parameter kept in another dtype or on another device goes to torch."""
+    return all(p.dtype == x.dtype and p.device == x.device for p in params)
+
+
 def rmsnorm(x, weight, eps=1e-6):
-    if hip.use_hip(x, "rmsnorm"):
+    if hip.use_hip(x, "rmsnorm") and _same_dtype_device(x, weight):
         return _HipRMSNorm.apply(x, weight, eps)
     return rmsnorm_torch(x, weight, eps)
 
@@ -81,6 +88,7 @@ class _HipAddRMSNorm(torch.autograd.Function):
         shape = x.shape
         x2d = x.contiguous().view(-1, shape[-1])
         r2d = residual.contiguous().view(-1, shape[-1])
+        weight = weight.contiguous()
         y, s, invrms = hip.ext().rmsnorm_fwd_add(x2d, r2d, weight, eps)
         ctx.save_for_backward(s, weight, invrms)
         ctx.shape = shape
@@ -104,7 +112,7 @@ def add_rmsnorm(x, residual, weight, eps=1e-6):
     """(normed, sum) where sum = x + residual, normed = rmsnorm(sum).
     Same bf16 rounding as the unfused composition."""
     if hip.use_hip(x, "rmsnorm") and x.dtype == torch.bfloat16 \
-            and residual.dtype == torch.bfloat16:
+            and _same_dtype_device(x, residual, weight):
         return _HipAddRMSNorm.apply(x, residual, weight, eps)
     s = x + residual
     return rmsnorm(s, weight, eps), s
@@ -119,6 +127,7 @@ class _HipLayerNorm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, eps):
         x2d = x.contiguous().view(-1, x.shape[-1])
+        weight, bias = weight.contiguous(), bias.contiguous()
         y, mean, invstd = hip.ext().layernorm_fwd(x2d, weight, bias, eps)
         ctx.save_for_backward(x2d, weight, mean, invstd)
         ctx.shape = x.shape
@@ -133,7 +142,7 @@ class _HipLayerNorm(torch.autograd.Function):
 
 
 def layernorm(x, weight, bias, eps=1e-5):
-    if hip.use_hip(x, "layernorm"):
+    if hip.use_hip(x, "layernorm") and _same_dtype_device(x, weight, bias):
         return _HipLayerNorm.apply(x, weight, bias, eps)
     return F.layer_norm(x, (x.shape[-1],), weight, bias, eps)
 
