@@ -119,6 +119,12 @@ torch::Tensor fused_fp8_gemm(torch::Tensor xq, torch::Tensor xs, torch::Tensor w
                              torch::Tensor bias, double lora_scale);
 std::vector<torch::Tensor> quantize_rows_fp8_scaled(torch::Tensor dy, torch::Tensor ws);
 torch::Tensor fused_fp8_gemm_dx(torch::Tensor gq, torch::Tensor gs, torch::Tensor wq, long K);
+torch::Tensor fused_fp8_gemm_ragged(torch::Tensor xq, torch::Tensor xs, torch::Tensor wq,
+                                    torch::Tensor ws, long N, torch::Tensor t,
+                                    torch::Tensor bw, torch::Tensor bias, double lora_scale);
+std::vector<torch::Tensor> quantize_rows_fp8_scaled_padded(torch::Tensor dy, torch::Tensor ws);
+torch::Tensor fused_fp8_gemm_dx_ragged(torch::Tensor gq, torch::Tensor gs, torch::Tensor wq,
+                                       long N, long K);
 // mxfp4_gemm.hip
 std::vector<torch::Tensor> quantize_rows_mxfp4(torch::Tensor x);
 torch::Tensor dequantize_rows_mxfp4(torch::Tensor codes, torch::Tensor scales, long R, long K,
@@ -238,6 +244,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "dx = (gq@wq)*sg on the f8f6f4 MFMA, W transposed in registers on the way to LDS, "
         "256^2 tile (gfx950)",
         py::arg("gq"), py::arg("gs"), py::arg("wq"), py::arg("K"));
+  // ragged output width (N no multiple of 256 / 128, e.g. llama_1b's gate/up at 5461)
+  m.def("fused_fp8_gemm_ragged", &fused_fp8_gemm_ragged,
+        "fused_fp8_gemm for any N >= 1: clamped edge block column, odd-pitch row stores (gfx950)",
+        py::arg("xq"), py::arg("xs"), py::arg("wq"), py::arg("ws"), py::arg("N"),
+        py::arg("t"), py::arg("bw"), py::arg("bias"), py::arg("lora_scale"));
+  m.def("quantize_rows_fp8_scaled_padded", &quantize_rows_fp8_scaled_padded,
+        "quantize_rows_fp8_scaled for any N >= 1 -> (codes uint8 [M, ceil128(N)] with zero pad "
+        "bytes, fp32 absmax [M]) (gfx950)",
+        py::arg("dy"), py::arg("ws"));
+  m.def("fused_fp8_gemm_dx_ragged", &fused_fp8_gemm_dx_ragged,
+        "fused_fp8_gemm_dx for any N >= 1 on the padded codes of the gradient; W rows past N "
+        "are neither read nor multiplied (gfx950)",
+        py::arg("gq"), py::arg("gs"), py::arg("wq"), py::arg("N"), py::arg("K"));
   m.def("quantize_rows_mxfp4", &quantize_rows_mxfp4,
         "bf16 [R,K] -> (e2m1 codes uint8 [R,Kp/2], E8M0 scales uint8 [R,Kp/32]), OCP MX "
         "blocks of 32 along K (gfx950)");

@@ -281,13 +281,19 @@ DEV_INLINE unsigned swz8(unsigned o) { return o ^ (((o >> 8) & 7u) << 4); }
 // 1-KiB pieces (8 full rows each), 4 per wave.  The LDS image is lane-linear
 // as glds requires; the per-lane GLOBAL source address carries the swizzle.
 // `gbase` is a byte pointer, `ld` the row pitch in bytes, `k0` a byte offset.
+// CLAMP: rows past `last` read row `last` instead (the edge tile of a ragged
+// operand: nothing outside the allocation is touched, the image rows hold
+// garbage that only feeds accumulators nobody stores).
+template <bool CLAMP = false>
 DEV_INLINE void stage_tile_bytes(char* image, const char* gbase, long row0, long ld,
-                                 long k0, int wave, int lane) {
+                                 long k0, int wave, int lane, long last = 0) {
 #pragma unroll
   for (int p4 = 0; p4 < 4; ++p4) {
     const int piece = wave * 4 + p4;
     const unsigned s = swz8(piece * 1024u + lane * 16u);  // source byte in tile
-    const char* src = gbase + (row0 + (s >> 7)) * ld + k0 + (s & 127u);
+    long row = row0 + (s >> 7);
+    if (CLAMP) row = row < last ? row : last;
+    const char* src = gbase + row * ld + k0 + (s & 127u);
     __builtin_amdgcn_global_load_lds(
         (const __attribute__((address_space(1))) unsigned int*)src,
         (__attribute__((address_space(3))) unsigned int*)(image) + (piece * 1024u) / 4,
@@ -313,6 +319,10 @@ DEV_INLINE bf16x8_q frag_bf16(const char* image, int row, int ks, int fq) {
 #define FP8_BUF_A(b) (smem + (b) * (2 * FP8_TILE_BYTES))
 #define FP8_BUF_B(b) (smem + (b) * (2 * FP8_TILE_BYTES) + FP8_TILE_BYTES)
 
+// RAGGED: any N >= 1.  The grid has ceil(N/256) block columns; in the last one
+// every W-side row index >= N (B tile, bw tile, wa, bias) is clamped to N-1,
+// and the epilogue stores rows of pitch N up to column N only.
+template <bool RAGGED>
 __global__ __launch_bounds__(512) void fused_fp8_gemm_kernel(
     const uint8_t* __restrict__ xq,         // [M,K] e4m3 codes
     const float* __restrict__ xa,           // [M] absmax of x rows
@@ -334,9 +344,10 @@ __global__ __launch_bounds__(512) void fused_fp8_gemm_kernel(
     const int xcd = wgid & 7, pos = wgid >> 3;
     wgid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + pos;
   }
-  const int nbn = (int)(N >> 8);
+  const int nbn = (int)((RAGGED ? N + 255 : N) >> 8);
   const long m0 = (long)(wgid / nbn) << 8;
   const long n0 = (long)(wgid % nbn) << 8;
+  const long nl = N - 1;  // last row of W (RAGGED clamps to it)
 
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -357,7 +368,7 @@ __global__ __launch_bounds__(512) void fused_fp8_gemm_kernel(
 
   const int KT = (int)(K >> 7);  // 128-k tiles
   stage_tile_bytes(FP8_BUF_A(0), xg, m0, K, 0, wave, lane);
-  stage_tile_bytes(FP8_BUF_B(0), wg, n0, K, 0, wave, lane);
+  stage_tile_bytes<RAGGED>(FP8_BUF_B(0), wg, n0, K, 0, wave, lane, nl);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
@@ -365,7 +376,8 @@ __global__ __launch_bounds__(512) void fused_fp8_gemm_kernel(
     const int cur = kt & 1;
     if (kt + 1 < KT) {
       stage_tile_bytes(FP8_BUF_A(cur ^ 1), xg, m0, K, (long)(kt + 1) << 7, wave, lane);
-      stage_tile_bytes(FP8_BUF_B(cur ^ 1), wg, n0, K, (long)(kt + 1) << 7, wave, lane);
+      stage_tile_bytes<RAGGED>(FP8_BUF_B(cur ^ 1), wg, n0, K, (long)(kt + 1) << 7, wave, lane,
+                               nl);
     }
     const char* A = FP8_BUF_A(cur);
     const char* B = FP8_BUF_B(cur);
@@ -392,8 +404,11 @@ __global__ __launch_bounds__(512) void fused_fp8_gemm_kernel(
   {
     float sw[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j)
-      sw[j] = __fdiv_rn(wa[n0 + wc * 64 + j * 16 + fr], FP8_MAX);
+    for (int j = 0; j < 4; ++j) {
+      long n = n0 + wc * 64 + j * 16 + fr;
+      if (RAGGED) n = n < nl ? n : nl;
+      sw[j] = __fdiv_rn(wa[n], FP8_MAX);
+    }
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       const f32x4_q ax =
@@ -412,7 +427,8 @@ __global__ __launch_bounds__(512) void fused_fp8_gemm_kernel(
 #pragma unroll 1
     for (int c = 0; c < RC; ++c) {
       stage_tile_bytes(FP8_BUF_A(c & 1), (const char*)t, m0, ldr, (long)c << 7, wave, lane);
-      stage_tile_bytes(FP8_BUF_B(c & 1), (const char*)bw, n0, ldr, (long)c << 7, wave, lane);
+      stage_tile_bytes<RAGGED>(FP8_BUF_B(c & 1), (const char*)bw, n0, ldr, (long)c << 7, wave,
+                               lane, nl);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
       const char* A = FP8_BUF_A(c & 1);
@@ -449,7 +465,11 @@ __global__ __launch_bounds__(512) void fused_fp8_gemm_kernel(
         const int row = i * 16 + fq * 4 + reg;  // within wave tile
         const int col = j * 16 + fr;
         float v = acc[i][j][reg];
-        if (bias) v += (float)bias[n0 + wc * 64 + col];
+        if (bias) {
+          long n = n0 + wc * 64 + col;
+          if (RAGGED) n = n < nl ? n : nl;
+          v += (float)bias[n];
+        }
         mine[row * 64 + col] = (__bf16)v;
       }
   // no barrier needed: each wave reads only its own region
@@ -458,7 +478,23 @@ __global__ __launch_bounds__(512) void fused_fp8_gemm_kernel(
     const int row = rr * 8 + (lane >> 3);          // 0..127
     const int cb = (lane & 7) * 8;                 // 8-col chunk
     const bf16x8_q vv = *reinterpret_cast<const bf16x8_q*>(mine + row * 64 + cb);
-    *reinterpret_cast<bf16x8_q*>(y + (m0 + wr * 128 + row) * N + n0 + wc * 64 + cb) = vv;
+    if (RAGGED) {
+      // pitch N: with N % 8 != 0 a row start is only 2-byte aligned, so the
+      // 16-byte store goes through Vec8 (alignof 2), as in norms.hip; the
+      // chunk that straddles N goes element by element, later ones are skipped
+      const long col = n0 + wc * 64 + cb;
+      __hip_bfloat16* dst = y + (m0 + wr * 128 + row) * N + col;
+      if (col + 8 <= N) {
+        store8(dst, *reinterpret_cast<const Vec8<__hip_bfloat16>*>(&vv));
+      } else {
+        const __hip_bfloat16* sv = reinterpret_cast<const __hip_bfloat16*>(&vv);
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+          if (col + e < N) dst[e] = sv[e];
+      }
+    } else {
+      *reinterpret_cast<bf16x8_q*>(y + (m0 + wr * 128 + row) * N + n0 + wc * 64 + cb) = vv;
+    }
   }
 }
 
@@ -485,19 +521,29 @@ static void check_fp8_bf16(const char* fn, const char* what, const torch::Tensor
 
 // xs / ws are the per-row absmax as quantize_rows_fp8 returns them; the
 // kernel turns them into scales (absmax/448) itself.
-torch::Tensor fused_fp8_gemm(torch::Tensor xq, torch::Tensor xs, torch::Tensor wq,
-                             torch::Tensor ws, long N, torch::Tensor t, torch::Tensor bw,
-                             torch::Tensor bias, double lora_scale) {
-  const char* fn = "fused_fp8_gemm";
+template <bool RAGGED>
+static torch::Tensor fused_fp8_gemm_impl(const char* fn, torch::Tensor xq, torch::Tensor xs,
+                                         torch::Tensor wq, torch::Tensor ws, long N,
+                                         torch::Tensor t, torch::Tensor bw, torch::Tensor bias,
+                                         double lora_scale) {
   TORCH_CHECK(xq.is_cuda(), fn, ": xq must be a GPU tensor");
   TORCH_CHECK(xq.dim() == 2, fn, ": xq must be 2-D [M, K]");
   const long M = xq.size(0), K = xq.size(1);
   TORCH_CHECK(M > 0 && K > 0 && N > 0, fn, ": M, N and K must be > 0");
-  TORCH_CHECK(M % 256 == 0 && N % 256 == 0 && K % 128 == 0, fn,
-              " requires M%256==0, N%256==0, K%128==0");
+  if (RAGGED) {
+    TORCH_CHECK(M % 256 == 0 && K % 128 == 0, fn, " requires M%256==0, K%128==0");
+    TORCH_CHECK(N < (1L << 31) && (M >> 8) * ((N + 255) >> 8) < (1L << 31), fn,
+                ": shape too large");
+  } else {
+    TORCH_CHECK(M % 256 == 0 && N % 256 == 0 && K % 128 == 0, fn,
+                " requires M%256==0, N%256==0, K%128==0");
+  }
   const auto dev = xq.device();
   check_fp8_operand(fn, "x", xq, xs, dev, M, K);
   check_fp8_operand(fn, "w", wq, ws, dev, N, K);
+  if (RAGGED)  // the glds staging reads 16 bytes a lane from both code tensors
+    TORCH_CHECK((uintptr_t)xq.data_ptr() % 16 == 0 && (uintptr_t)wq.data_ptr() % 16 == 0, fn,
+                ": code tensors must be 16-byte aligned");
   int r = 0;
   torch::Tensor t_scaled;
   if (t.defined() && t.numel() > 0) {
@@ -521,9 +567,9 @@ torch::Tensor fused_fp8_gemm(torch::Tensor xq, torch::Tensor xs, torch::Tensor w
   }
   auto y = torch::empty({M, N}, xq.options().dtype(torch::kBFloat16));
   auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
-  dim3 grid((unsigned)((M >> 8) * (N >> 8))), block(512);
+  dim3 grid((unsigned)((M >> 8) * ((RAGGED ? N + 255 : N) >> 8))), block(512);
   const size_t smem = 4 * FP8_TILE_BYTES;  // 128 KiB
-  hipLaunchKernelGGL(fused_fp8_gemm_kernel, grid, block, smem, stream,
+  hipLaunchKernelGGL(fused_fp8_gemm_kernel<RAGGED>, grid, block, smem, stream,
                      xq.data_ptr<uint8_t>(), xs.data_ptr<float>(), wq.data_ptr<uint8_t>(),
                      ws.data_ptr<float>(),
                      r > 0 ? (const __hip_bfloat16*)t_scaled.data_ptr() : nullptr,
@@ -531,6 +577,21 @@ torch::Tensor fused_fp8_gemm(torch::Tensor xq, torch::Tensor xs, torch::Tensor w
                      (__hip_bfloat16*)y.data_ptr(), M, N, K, r);
   HIP_CHECK_LAST();
   return y;
+}
+
+torch::Tensor fused_fp8_gemm(torch::Tensor xq, torch::Tensor xs, torch::Tensor wq,
+                             torch::Tensor ws, long N, torch::Tensor t, torch::Tensor bw,
+                             torch::Tensor bias, double lora_scale) {
+  return fused_fp8_gemm_impl<false>("fused_fp8_gemm", xq, xs, wq, ws, N, t, bw, bias,
+                                    lora_scale);
+}
+
+// fused_fp8_gemm for any N >= 1 (llama_1b's gate/up: N = 5461); y has pitch N
+torch::Tensor fused_fp8_gemm_ragged(torch::Tensor xq, torch::Tensor xs, torch::Tensor wq,
+                                    torch::Tensor ws, long N, torch::Tensor t,
+                                    torch::Tensor bw, torch::Tensor bias, double lora_scale) {
+  return fused_fp8_gemm_impl<true>("fused_fp8_gemm_ragged", xq, xs, wq, ws, N, t, bw, bias,
+                                   lora_scale);
 }
 
 
@@ -588,16 +649,44 @@ DEV_INLINE uint4 unitf_encode(const Unit16f& g, float inv) {
 // Geometry of quantize_rows_fp8_kernel; the scaled fp32 units (16 VGPRs each)
 // stay in registers between the max reduction and the conversion.  NU == 0
 // loops (N > 8192) and rebuilds g from L2 in the second pass.
-template <int G, int NU>
+// Unit c of a row of any length N, for the padded form: units wholly below N
+// load like the aligned kernel's but through a 2-byte-aligned type (rows of
+// odd N start anywhere), the unit that straddles N loads dy and ws element by
+// element, units at or past N are zeros.
+DEV_INLINE Unit16f unit_scale_ragged(const __hip_bfloat16* __restrict__ xrow,
+                                     const float* __restrict__ ws, int c, int N) {
+  Unit16f g;
+  if (c * 16 + 16 <= N) {
+    const Vec8<__hip_bfloat16> a = load8(xrow + c * 16), b = load8(xrow + c * 16 + 8);
+    Unit16 u;
+    __builtin_memcpy(&u.lo, &a, 16);
+    __builtin_memcpy(&u.hi, &b, 16);
+    g = unit_scale(u, ws + c * 16);
+  } else {
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      const int n = c * 16 + e;
+      g.v[e] = n < N ? __fmul_rn(to_f32(xrow[n]), __fdiv_rn(ws[n], FP8_MAX)) : 0.f;
+    }
+  }
+  return g;
+}
+
+// PAD: any N >= 1; the code rows have pitch Np = N rounded up to 128 and the
+// bytes [N, Np) are zero codes, so the rows are 16-byte aligned glds sources
+// and whole 128-deep reduction tiles for fused_fp8_gemm_dx_kernel<true>.
+template <int G, int NU, bool PAD>
 __global__ __launch_bounds__(256) void quantize_rows_fp8_scaled_kernel(
     const __hip_bfloat16* __restrict__ x, const float* __restrict__ ws,
     uint8_t* __restrict__ q, float* __restrict__ absmax, long R, int N) {
   const int gl = threadIdx.x & (G - 1);
   const long row = ((long)blockIdx.x * 256 + threadIdx.x) / G;
   const bool live = row < R;  // whole lane groups: shuffles stay inside a row
-  const int units = N >> 4;
-  const Unit16* src = reinterpret_cast<const Unit16*>(x + (live ? row : 0) * N);
-  uint4* dst = reinterpret_cast<uint4*>(q + (live ? row : 0) * N);
+  const int Np = PAD ? (N + 127) & ~127 : N;
+  const int units = Np >> 4;
+  const __hip_bfloat16* xrow = x + (live ? row : 0) * N;
+  const Unit16* src = reinterpret_cast<const Unit16*>(xrow);
+  uint4* dst = reinterpret_cast<uint4*>(q + (live ? row : 0) * Np);
   float am = 0.f;
   if (NU > 0) {
     Unit16f g[NU > 0 ? NU : 1];
@@ -605,7 +694,7 @@ __global__ __launch_bounds__(256) void quantize_rows_fp8_scaled_kernel(
     for (int i = 0; i < NU; ++i) {
       const int c = gl + i * G;
       if (live && c < units) {
-        g[i] = unit_scale(src[c], ws + c * 16);
+        g[i] = PAD ? unit_scale_ragged(xrow, ws, c, N) : unit_scale(src[c], ws + c * 16);
       } else {
 #pragma unroll
         for (int e = 0; e < 16; ++e) g[i].v[e] = 0.f;
@@ -622,61 +711,74 @@ __global__ __launch_bounds__(256) void quantize_rows_fp8_scaled_kernel(
   } else {
     if (live)
       for (int c = gl; c < units; c += G)
-        am = fmaxf(am, unitf_absmax(unit_scale(src[c], ws + c * 16)));
+        am = fmaxf(am, unitf_absmax(PAD ? unit_scale_ragged(xrow, ws, c, N)
+                                        : unit_scale(src[c], ws + c * 16)));
     am = group_max<G>(am);
     const float inv = am > 0.f ? __fdiv_rn(FP8_MAX, am) : 0.f;
     if (live)
       for (int c = gl; c < units; c += G)
-        dst[c] = unitf_encode(unit_scale(src[c], ws + c * 16), inv);
+        dst[c] = unitf_encode(PAD ? unit_scale_ragged(xrow, ws, c, N)
+                                  : unit_scale(src[c], ws + c * 16), inv);
   }
   if (live && gl == 0) absmax[row] = am;
 }
 
-template <int G, int NU>
+template <int G, int NU, bool PAD = false>
 static void launch_quantize_scaled(const torch::Tensor& x, const torch::Tensor& ws,
                                    torch::Tensor& q, torch::Tensor& am, long R, int N,
                                    hipStream_t stream) {
   const long rows_per_block = 256 / G;
   dim3 grid((unsigned)((R + rows_per_block - 1) / rows_per_block)), block(256);
-  hipLaunchKernelGGL((quantize_rows_fp8_scaled_kernel<G, NU>), grid, block, 0, stream,
+  hipLaunchKernelGGL((quantize_rows_fp8_scaled_kernel<G, NU, PAD>), grid, block, 0, stream,
                      (const __hip_bfloat16*)x.data_ptr(), ws.data_ptr<float>(),
                      q.data_ptr<uint8_t>(), am.data_ptr<float>(), R, N);
 }
 
 // dy [M,N] bf16, ws [N] = the absmax of W's rows as QuantizedWeight keeps them
-std::vector<torch::Tensor> quantize_rows_fp8_scaled(torch::Tensor dy, torch::Tensor ws) {
-  const char* fn = "quantize_rows_fp8_scaled";
+template <bool PAD>
+static std::vector<torch::Tensor> quantize_rows_fp8_scaled_impl(const char* fn, torch::Tensor dy,
+                                                                torch::Tensor ws) {
   TORCH_CHECK(dy.is_cuda(), fn, ": dy must be a GPU tensor");
   TORCH_CHECK(dy.dim() == 2, fn, ": dy must be 2-D [M, N]");
   TORCH_CHECK(dy.is_contiguous(), fn, ": dy must be contiguous");
   TORCH_CHECK(dy.scalar_type() == torch::kBFloat16, fn, ": dy must be bf16");
   const long R = dy.size(0), N = dy.size(1);
   TORCH_CHECK(R > 0 && N > 0, fn, ": M and N must be > 0");
-  TORCH_CHECK(N % 16 == 0, fn, ": N must be a multiple of 16");
-  TORCH_CHECK(N < (1L << 31) && R < (1L << 31) * 4, fn, ": shape too large");
+  if (!PAD) TORCH_CHECK(N % 16 == 0, fn, ": N must be a multiple of 16");
+  TORCH_CHECK(N < (1L << 31) - (PAD ? 128 : 0) && R < (1L << 31) * 4, fn, ": shape too large");
   TORCH_CHECK(ws.device() == dy.device(), fn, ": ws must be on dy's device");
   TORCH_CHECK(ws.scalar_type() == torch::kFloat32, fn, ": ws must be fp32");
   TORCH_CHECK(ws.is_contiguous(), fn, ": ws must be contiguous");
   TORCH_CHECK(ws.numel() == N, fn, ": ws must hold one value per column of dy");
-  auto q = torch::empty({R, N}, dy.options().dtype(torch::kUInt8));
+  const long Np = PAD ? (N + 127) / 128 * 128 : N;  // the form is chosen by the padded width
+  auto q = torch::empty({R, Np}, dy.options().dtype(torch::kUInt8));
   auto am = torch::empty({R}, dy.options().dtype(torch::kFloat32));
   auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
   const int n = (int)N;
-  if (N <= 256) {
-    launch_quantize_scaled<16, 1>(dy, ws, q, am, R, n, stream);
-  } else if (N <= 1024) {
-    launch_quantize_scaled<64, 1>(dy, ws, q, am, R, n, stream);
-  } else if (N <= 2048) {
-    launch_quantize_scaled<64, 2>(dy, ws, q, am, R, n, stream);
-  } else if (N <= 4096) {
-    launch_quantize_scaled<64, 4>(dy, ws, q, am, R, n, stream);
-  } else if (N <= 8192) {
-    launch_quantize_scaled<64, 8>(dy, ws, q, am, R, n, stream);
+  if (Np <= 256) {
+    launch_quantize_scaled<16, 1, PAD>(dy, ws, q, am, R, n, stream);
+  } else if (Np <= 1024) {
+    launch_quantize_scaled<64, 1, PAD>(dy, ws, q, am, R, n, stream);
+  } else if (Np <= 2048) {
+    launch_quantize_scaled<64, 2, PAD>(dy, ws, q, am, R, n, stream);
+  } else if (Np <= 4096) {
+    launch_quantize_scaled<64, 4, PAD>(dy, ws, q, am, R, n, stream);
+  } else if (Np <= 8192) {
+    launch_quantize_scaled<64, 8, PAD>(dy, ws, q, am, R, n, stream);
   } else {
-    launch_quantize_scaled<64, 0>(dy, ws, q, am, R, n, stream);
+    launch_quantize_scaled<64, 0, PAD>(dy, ws, q, am, R, n, stream);
   }
   HIP_CHECK_LAST();
   return {q, am};
+}
+
+std::vector<torch::Tensor> quantize_rows_fp8_scaled(torch::Tensor dy, torch::Tensor ws) {
+  return quantize_rows_fp8_scaled_impl<false>("quantize_rows_fp8_scaled", dy, ws);
+}
+
+// any N >= 1: codes [M, Np], Np = N rounded up to 128, the pad bytes zero codes
+std::vector<torch::Tensor> quantize_rows_fp8_scaled_padded(torch::Tensor dy, torch::Tensor ws) {
+  return quantize_rows_fp8_scaled_impl<true>("quantize_rows_fp8_scaled_padded", dy, ws);
 }
 
 // ---------------------------------------------------------------------------
@@ -736,6 +838,30 @@ DEV_INLINE void write_b_patch(char* image, const unsigned (&st)[16], int pq, int
   }
 }
 
+// The patch of a reduction tile that holds only `nv` < 128 rows of W (the last
+// tile of a ragged N).  Rows at or past nv read row nv-1 instead, so no byte
+// outside W is touched; the lane offsets stay 32-bit (127*K + 252 < 2^31).
+DEV_INLINE void load_b_patch_edge(unsigned (&st)[16], const char* tile, unsigned K, int pq,
+                                  int pc, int nv) {
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const int n = pc * 16 + i;
+    const unsigned off = (unsigned)(n < nv ? n : nv - 1) * K + (unsigned)(pq * 4);
+    st[i] = *reinterpret_cast<const unsigned*>(tile + off);
+  }
+}
+
+// ... and their registers are cleared before the transposition: the clamped
+// loads hold codes of a real row, and 0 x NaN-code would not be 0
+DEV_INLINE void zero_b_patch_edge(unsigned (&st)[16], int pc, int nv) {
+#pragma unroll
+  for (int i = 0; i < 16; ++i)
+    if (pc * 16 + i >= nv) st[i] = 0u;
+}
+
+// RAGGED: any N >= 1.  gq has pitch Np = N rounded up to 128 with zero codes
+// in [N, Np) (quantize_rows_fp8_scaled_padded), wq holds N rows.
+template <bool RAGGED>
 __global__ __launch_bounds__(512) void fused_fp8_gemm_dx_kernel(
     const uint8_t* __restrict__ gq,    // [M,N] e4m3 codes of dy*diag(sw)
     const float* __restrict__ ga,      // [M] absmax of its rows
@@ -779,9 +905,17 @@ __global__ __launch_bounds__(512) void fused_fp8_gemm_dx_kernel(
   const char* wg = (const char*)wq + k0;
   unsigned st[16];
 
-  const int NT = (int)(N >> 7);  // 128-n tiles
-  stage_tile_bytes(FP8_BUF_A(0), gg, m0, N, 0, wave, lane);
-  load_b_patch(st, wg, K, voff);
+  const long ND = RAGGED ? (N + 127) & ~127L : N;  // pitch of gq, reduction depth
+  const int NT = (int)(ND >> 7);                   // 128-n tiles
+  // rows of W in the last tile; < 128 only when RAGGED
+  const int nv = RAGGED ? (int)(N - ((long)(NT - 1) << 7)) : 128;
+  stage_tile_bytes(FP8_BUF_A(0), gg, m0, ND, 0, wave, lane);
+  if (RAGGED && NT == 1 && nv < 128) {
+    load_b_patch_edge(st, wg, (unsigned)K, pq, pc, nv);
+    zero_b_patch_edge(st, pc, nv);
+  } else {
+    load_b_patch(st, wg, K, voff);
+  }
   write_b_patch(FP8_BUF_B(0), st, pq, pc);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
@@ -789,13 +923,21 @@ __global__ __launch_bounds__(512) void fused_fp8_gemm_dx_kernel(
   for (int nt = 0; nt < NT; ++nt) {
     const int cur = nt & 1;
     const bool more = nt + 1 < NT;
+    const bool edge = RAGGED && nt + 2 == NT && nv < 128;  // uniform: next tile is short
     if (more) {
-      stage_tile_bytes(FP8_BUF_A(cur ^ 1), gg, m0, N, (long)(nt + 1) << 7, wave, lane);
-      // keep the lane offset a 32-bit VGPR next to scalar row bases (saddr
-      // form): hoisted out of the loop it becomes 16 64-bit lane addresses
-      unsigned vo = voff;
-      asm volatile("" : "+v"(vo));
-      load_b_patch(st, wg + ((long)(nt + 1) << 7) * K, K, vo);
+      stage_tile_bytes(FP8_BUF_A(cur ^ 1), gg, m0, ND, (long)(nt + 1) << 7, wave, lane);
+      const char* tile = wg + ((long)(nt + 1) << 7) * K;
+      if (edge) {
+        int q4 = pq;  // opaque like vo below, so the 16 offsets are not hoisted
+        asm volatile("" : "+v"(q4));
+        load_b_patch_edge(st, tile, (unsigned)K, q4, pc, nv);
+      } else {
+        // keep the lane offset a 32-bit VGPR next to scalar row bases (saddr
+        // form): hoisted out of the loop it becomes 16 64-bit lane addresses
+        unsigned vo = voff;
+        asm volatile("" : "+v"(vo));
+        load_b_patch(st, tile, K, vo);
+      }
     }
     const char* A = FP8_BUF_A(cur);
     const char* B = FP8_BUF_B(cur);
@@ -815,6 +957,7 @@ __global__ __launch_bounds__(512) void fused_fp8_gemm_dx_kernel(
     __builtin_amdgcn_s_setprio(0);
     // the other B image was last read in the previous iteration, behind its
     // barrier; the patch loads had the whole MFMA loop to land
+    if (edge) zero_b_patch_edge(st, pc, nv);
     if (more) write_b_patch(FP8_BUF_B(cur ^ 1), st, pq, pc);
     // drain next tile's glds, then release the buffers we just read
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -848,19 +991,27 @@ __global__ __launch_bounds__(512) void fused_fp8_gemm_dx_kernel(
   }
 }
 
-// gq / gs: quantize_rows_fp8_scaled(dy, W's absmax); wq: W's codes [N,K]
-torch::Tensor fused_fp8_gemm_dx(torch::Tensor gq, torch::Tensor gs, torch::Tensor wq, long K) {
-  const char* fn = "fused_fp8_gemm_dx";
+// N: rows of W.  Aligned: gq is [M,N].  RAGGED: gq is [M,Np], Np = N rounded up to 128.
+template <bool RAGGED>
+static torch::Tensor fused_fp8_gemm_dx_impl(const char* fn, torch::Tensor gq, torch::Tensor gs,
+                                            torch::Tensor wq, long N, long K) {
   TORCH_CHECK(gq.is_cuda(), fn, ": gq must be a GPU tensor");
-  TORCH_CHECK(gq.dim() == 2, fn, ": gq must be 2-D [M, N]");
-  const long M = gq.size(0), N = gq.size(1);
+  TORCH_CHECK(gq.dim() == 2, fn, RAGGED ? ": gq must be 2-D [M, Np]" : ": gq must be 2-D [M, N]");
+  const long M = gq.size(0), ND = gq.size(1);
+  if (!RAGGED) N = ND;
   TORCH_CHECK(M > 0 && N > 0 && K > 0, fn, ": M, N and K must be > 0");
-  TORCH_CHECK(M % 256 == 0 && K % 256 == 0 && N % 128 == 0, fn,
-              " requires M%256==0, K%256==0, N%128==0");
+  if (RAGGED) {
+    TORCH_CHECK(M % 256 == 0 && K % 256 == 0, fn, " requires M%256==0, K%256==0");
+    TORCH_CHECK(N < (1L << 31) - 128, fn, ": shape too large");
+    TORCH_CHECK(ND == (N + 127) / 128 * 128, fn, ": gq must have N rounded up to 128 columns");
+  } else {
+    TORCH_CHECK(M % 256 == 0 && K % 256 == 0 && N % 128 == 0, fn,
+                " requires M%256==0, K%256==0, N%128==0");
+  }
   TORCH_CHECK(K < (1L << 24) && N < (1L << 31) && (M >> 8) * (K >> 8) < (1L << 31), fn,
               ": shape too large");
   const auto dev = gq.device();
-  check_fp8_operand(fn, "g", gq, gs, dev, M, N);
+  check_fp8_operand(fn, "g", gq, gs, dev, M, ND);
   TORCH_CHECK(wq.is_cuda() && wq.device() == dev, fn, ": w codes must be on gq's GPU");
   TORCH_CHECK(wq.scalar_type() == torch::kUInt8, fn, ": w codes must be uint8");
   TORCH_CHECK(wq.is_contiguous(), fn, ": w codes must be contiguous");
@@ -871,11 +1022,22 @@ torch::Tensor fused_fp8_gemm_dx(torch::Tensor gq, torch::Tensor gs, torch::Tenso
   auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
   dim3 grid((unsigned)((M >> 8) * (K >> 8))), block(512);
   const size_t smem = 4 * FP8_TILE_BYTES;  // 128 KiB
-  hipLaunchKernelGGL(fused_fp8_gemm_dx_kernel, grid, block, smem, stream,
+  hipLaunchKernelGGL(fused_fp8_gemm_dx_kernel<RAGGED>, grid, block, smem, stream,
                      gq.data_ptr<uint8_t>(), gs.data_ptr<float>(), wq.data_ptr<uint8_t>(),
                      (__hip_bfloat16*)dx.data_ptr(), M, N, K);
   HIP_CHECK_LAST();
   return dx;
+}
+
+// gq / gs: quantize_rows_fp8_scaled(dy, W's absmax); wq: W's codes [N,K]
+torch::Tensor fused_fp8_gemm_dx(torch::Tensor gq, torch::Tensor gs, torch::Tensor wq, long K) {
+  return fused_fp8_gemm_dx_impl<false>("fused_fp8_gemm_dx", gq, gs, wq, 0, K);
+}
+
+// gq / gs: quantize_rows_fp8_scaled_padded(dy, W's absmax), [M, ceil128(N)]; wq: [N,K]
+torch::Tensor fused_fp8_gemm_dx_ragged(torch::Tensor gq, torch::Tensor gs, torch::Tensor wq,
+                                       long N, long K) {
+  return fused_fp8_gemm_dx_impl<true>("fused_fp8_gemm_dx_ragged", gq, gs, wq, N, K);
 }
 
 #if defined(__HIP_DEVICE_COMPILE__)

@@ -809,6 +809,13 @@ class _FusedLoRALinear(torch.autograd.Function):
                 dA, dB, None, None, None)
 
 
+# fp8 frozen W whose out_features is no multiple of 256 (forward) / 128 (dx),
+# e.g. llama_1b's gate/up at 5461: the ragged variants of the fp8 GEMMs
+# (ops/csrc/fp8_gemm.hip).  RELORA_AMD_FP8_RAGGED=0 sends those shapes back to
+# the materialize arm.
+_FP8_RAGGED = os.environ.get("RELORA_AMD_FP8_RAGGED", "1") != "0"
+
+
 class _QuantizedLoRALinear(torch.autograd.Function):
     """K15 path: frozen W stays NF4/int8/fp8/MXFP4-packed end to end.  Forward
     runs the dequant-fused MFMA GEMM (aligned NF4/int8 shapes), the fp8- or
@@ -842,7 +849,17 @@ class _QuantizedLoRALinear(torch.autograd.Function):
         fused_nf4 = aligned and qw.mode == "4bit" and K % 64 == 0
         fused_i8 = aligned and qw.mode == "8bit" and K % 256 == 0
         fused_fp8 = aligned and qw.mode == "fp8" and K % 128 == 0
-        if fused_fp8:
+        ragged_fp8 = (_FP8_RAGGED and qw.mode == "fp8" and M % 256 == 0 and K % 128 == 0
+                      and r % 64 == 0 and r <= 256 and _FUSED_K1 != "0" and N % 256 != 0)
+        if ragged_fp8:
+            # the fused arm below for any N: edge block column clamped, rows of
+            # pitch N stored up to column N
+            xq, xs = hip.ext().quantize_rows_fp8(x2d)
+            y = hip.ext().fused_fp8_gemm_ragged(
+                xq, xs, qw.qdata, qw.absmax, N, t_u, lora_B,
+                bias if bias is not None else empty, scale)
+            del xq, xs
+        elif fused_fp8:
             # activations quantised per token row, GEMM on the e4m3 codes;
             # the unaligned arm below multiplies bf16 activations instead
             xq, xs = hip.ext().quantize_rows_fp8(x2d)
@@ -898,6 +915,13 @@ class _QuantizedLoRALinear(torch.autograd.Function):
             # token row, dx on the e4m3 codes of W as stored (no dense W)
             gq, gs = hip.ext().quantize_rows_fp8_scaled(dy2d, qw.absmax)
             dx = hip.ext().fused_fp8_gemm_dx(gq, gs, qw.qdata, K)
+            del gq, gs
+        elif (ctx.fp8_backward and _FP8_RAGGED and qw.mode == "fp8" and M % 256 == 0
+                and K % 256 == 0 and _FUSED_K1 != "0"):
+            # N % 128 != 0: g's code rows padded with zero codes to whole
+            # reduction tiles, W's missing rows zeroed in registers
+            gq, gs = hip.ext().quantize_rows_fp8_scaled_padded(dy2d, qw.absmax)
+            dx = hip.ext().fused_fp8_gemm_dx_ragged(gq, gs, qw.qdata, N, K)
             del gq, gs
         else:
             w = qw.materialize(torch.bfloat16)  # transient dense W for dX only
