@@ -46,6 +46,7 @@
 #include <torch/extension.h>
 
 #include "common.h"
+#include "gemm_host.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_q;
 typedef __attribute__((ext_vector_type(4))) float f32x4_q;
@@ -512,13 +513,6 @@ static void check_fp8_operand(const char* fn, const char* what, const torch::Ten
   TORCH_CHECK(a.numel() == rows, fn, ": ", what, " absmax must hold one value per row");
 }
 
-static void check_fp8_bf16(const char* fn, const char* what, const torch::Tensor& v,
-                           const torch::Device& dev) {
-  TORCH_CHECK(v.device() == dev, fn, ": ", what, " must be on xq's device");
-  TORCH_CHECK(v.scalar_type() == torch::kBFloat16, fn, ": ", what, " must be bf16");
-  TORCH_CHECK(v.is_contiguous(), fn, ": ", what, " must be contiguous");
-}
-
 // xs / ws are the per-row absmax as quantize_rows_fp8 returns them; the
 // kernel turns them into scales (absmax/448) itself.
 template <bool RAGGED>
@@ -544,27 +538,7 @@ static torch::Tensor fused_fp8_gemm_impl(const char* fn, torch::Tensor xq, torch
   if (RAGGED)  // the glds staging reads 16 bytes a lane from both code tensors
     TORCH_CHECK((uintptr_t)xq.data_ptr() % 16 == 0 && (uintptr_t)wq.data_ptr() % 16 == 0, fn,
                 ": code tensors must be 16-byte aligned");
-  int r = 0;
-  torch::Tensor t_scaled;
-  if (t.defined() && t.numel() > 0) {
-    check_fp8_bf16(fn, "t", t, dev);
-    TORCH_CHECK(t.dim() == 2 && t.size(0) == M, fn, ": t must be [M, r]");
-    r = (int)t.size(1);
-    TORCH_CHECK(t.size(1) % 64 == 0 && t.size(1) <= 256, fn,
-                ": r must be a multiple of 64, <= 256");
-    TORCH_CHECK(bw.defined(), fn, ": bw is required with t");
-    check_fp8_bf16(fn, "bw", bw, dev);
-    TORCH_CHECK(bw.dim() == 2 && bw.size(0) == N && bw.size(1) == r, fn,
-                ": bw must be [N, r]");
-    // fold the LoRA scale into t, as the other fused GEMMs do
-    t_scaled = (lora_scale == 1.0) ? t : (t * lora_scale).contiguous();
-  }
-  const __hip_bfloat16* bias_p = nullptr;
-  if (bias.defined() && bias.numel() > 0) {
-    check_fp8_bf16(fn, "bias", bias, dev);
-    TORCH_CHECK(bias.numel() == N, fn, ": bias must have N elements");
-    bias_p = (const __hip_bfloat16*)bias.data_ptr();
-  }
+  const LoraArgs a = prep_lora_bias(fn, "xq", dev, t, bw, bias, M, N, 64, 256, lora_scale);
   auto y = torch::empty({M, N}, xq.options().dtype(torch::kBFloat16));
   auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
   dim3 grid((unsigned)((M >> 8) * ((RAGGED ? N + 255 : N) >> 8))), block(512);
@@ -572,9 +546,7 @@ static torch::Tensor fused_fp8_gemm_impl(const char* fn, torch::Tensor xq, torch
   hipLaunchKernelGGL(fused_fp8_gemm_kernel<RAGGED>, grid, block, smem, stream,
                      xq.data_ptr<uint8_t>(), xs.data_ptr<float>(), wq.data_ptr<uint8_t>(),
                      ws.data_ptr<float>(),
-                     r > 0 ? (const __hip_bfloat16*)t_scaled.data_ptr() : nullptr,
-                     r > 0 ? (const __hip_bfloat16*)bw.data_ptr() : nullptr, bias_p,
-                     (__hip_bfloat16*)y.data_ptr(), M, N, K, r);
+                     a.t, a.bw, a.bias, (__hip_bfloat16*)y.data_ptr(), M, N, K, a.r);
   HIP_CHECK_LAST();
   return y;
 }

@@ -26,15 +26,14 @@
 #include <ATen/hip/HIPContext.h>
 #include <torch/extension.h>
 
-#include "common.h"
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_g;
-typedef __attribute__((ext_vector_type(4))) float f32x4_g;
+#include "gemm_host.h"
+#include "gemm_tile.h"
 
 // ---------------------------------------------------------------------------
-// Host checks shared by the five entry points.  The kernels index every
-// operand from M, N, K and r alone, so whatever is not checked here is read
-// out of bounds on a mismatch.  All of them run before the launch.
+// Host checks of x and the W operand.  The kernels index every operand from
+// M, N, K and r alone, so whatever is not checked here or in prep_lora_bias
+// (gemm_host.h) is read out of bounds on a mismatch.  All of them run before
+// the launch.
 // ---------------------------------------------------------------------------
 
 static void check_x(const char* fn, const torch::Tensor& x) {
@@ -72,43 +71,88 @@ static void check_quant_w(const char* fn, const torch::Tensor& x,
               ": absmax must hold N*K/", block, " values");
 }
 
-// Returns r (0 without LoRA).  Runs before the lora_scale == 1.0 shortcut
-// that hands `t` to the kernel as it came.
-static int check_lora(const char* fn, const torch::Tensor& x,
-                      const torch::Tensor& t, const torch::Tensor& bw,
-                      long M, long N, int r_step, int r_max) {
-  if (!(t.defined() && t.numel() > 0)) return 0;
-  TORCH_CHECK(t.device() == x.device(), fn, ": t must be on x's device");
-  TORCH_CHECK(t.scalar_type() == torch::kBFloat16, fn, ": t must be bf16");
-  TORCH_CHECK(t.is_contiguous(), fn, ": t must be contiguous");
-  TORCH_CHECK(t.dim() == 2 && t.size(0) == M, fn, ": t must be [M, r]");
-  const long r = t.size(1);
-  TORCH_CHECK(r % r_step == 0 && r <= r_max, fn, ": r must be a multiple of ",
-              r_step, ", <= ", r_max);
-  TORCH_CHECK(bw.defined() && bw.device() == x.device(), fn,
-              ": bw must be on x's device");
-  TORCH_CHECK(bw.scalar_type() == torch::kBFloat16, fn, ": bw must be bf16");
-  TORCH_CHECK(bw.is_contiguous(), fn, ": bw must be contiguous");
-  TORCH_CHECK(bw.dim() == 2 && bw.size(0) == N && bw.size(1) == r, fn,
-              ": bw must be [N, r]");
-  return (int)r;
+// Everything behind an entry point's shape rule and W-operand checks: the
+// LoRA / bias arguments, y, and the launch of `kernel` on (M/256) x (N/tile_n)
+// work-groups.  `w...` are the kernel's W-operand pointers, which it takes
+// between x and t.
+template <typename Kernel, typename... W>
+static torch::Tensor launch_fused(const char* fn, Kernel kernel, const torch::Tensor& x, long N,
+                                  int tile_n, size_t smem, int r_step, int r_max,
+                                  const torch::Tensor& t, const torch::Tensor& bw,
+                                  const torch::Tensor& bias, double lora_scale, W... w) {
+  const long M = x.size(0), K = x.size(1);
+  const LoraArgs a = prep_lora_bias(fn, "x", x.device(), t, bw, bias, M, N, r_step, r_max,
+                                    lora_scale);
+  auto y = torch::empty({M, N}, x.options());
+  auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
+  dim3 grid((M >> 8) * (N / tile_n));
+  dim3 block(512);
+  hipLaunchKernelGGL(kernel, grid, block, smem, stream, (const __hip_bfloat16*)x.data_ptr(), w...,
+                     a.t, a.bw, a.bias, (__hip_bfloat16*)y.data_ptr(), M, N, K, a.r);
+  HIP_CHECK_LAST();
+  return y;
 }
 
-// Returns the bias pointer, or null for an undefined / empty bias.
-static const __hip_bfloat16* check_bias(const char* fn, const torch::Tensor& x,
-                                        const torch::Tensor& bias, long N) {
-  if (!(bias.defined() && bias.numel() > 0)) return nullptr;
-  TORCH_CHECK(bias.device() == x.device(), fn, ": bias must be on x's device");
-  TORCH_CHECK(bias.scalar_type() == torch::kBFloat16, fn, ": bias must be bf16");
-  TORCH_CHECK(bias.is_contiguous(), fn, ": bias must be contiguous");
-  TORCH_CHECK(bias.numel() == N, fn, ": bias must have N elements");
-  return (const __hip_bfloat16*)bias.data_ptr();
+// LDS of the 2-buffer kernels: [2][A 256x64 | B 256x64] bf16 = 128 KiB
+#define TILE_BYTES (256 * 64 * 2)
+#define BUF_A(b) (smem + (b) * (2 * TILE_BYTES))
+#define BUF_B(b) (smem + (b) * (2 * TILE_BYTES) + TILE_BYTES)
+
+__global__ __launch_bounds__(512) void fused_lora_gemm_kernel(
+    const __hip_bfloat16* __restrict__ x,   // [M,K]
+    const __hip_bfloat16* __restrict__ w,   // [N,K]
+    const __hip_bfloat16* __restrict__ t,   // [M,r] or null (pre-scaled)
+    const __hip_bfloat16* __restrict__ bw,  // [N,r] or null
+    const __hip_bfloat16* __restrict__ bias,  // [N] or null
+    __hip_bfloat16* __restrict__ y,         // [M,N]
+    long M, long N, long K, int r) {
+  // one __shared__ array only (glds pipeline rule)
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+
+  const int wgid = xcd_remap();
+  const int nbn = (int)(N >> 8);
+  const long m0 = (long)(wgid / nbn) << 8;
+  const long n0 = (long)(wgid % nbn) << 8;
+  const WaveCoord wv = wave_coord();
+
+  f32x4 acc[8][4];
+  zero_acc(acc);
+
+  const int KT = (int)(K >> 6);
+  stage_glds(BUF_A(0), x, m0, K, 0, wv);
+  stage_glds(BUF_B(0), w, n0, K, 0, wv);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+
+  for (int kt = 0; kt < KT; ++kt) {
+    const int cur = kt & 1;
+    if (kt + 1 < KT) {
+      stage_glds(BUF_A(cur ^ 1), x, m0, K, (kt + 1) << 6, wv);
+      stage_glds(BUF_B(cur ^ 1), w, n0, K, (kt + 1) << 6, wv);
+    }
+    mma_bf16_chunk(acc, BUF_A(cur), BUF_B(cur), wv);
+    // drain next tile's glds, then release the buffers we just read
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+  }
+
+  // r<=128: both operands fit the 4 buffer slots at once
+  lora_update(acc, t, bw, m0, n0, r, BUF_A(0), BUF_B(0), 2 * TILE_BYTES, wv);
+
+  __syncthreads();
+  store_wave_tile((__bf16*)smem + wv.wave * (128 * 64) /* 16 KiB per wave */, acc, bias, y,
+                     m0, N, n0, wv);
 }
 
-// st_16x32 swizzle on a byte offset within a [rows][64] bf16 image
-// (128-B rows): byte bit5 ^= bit9 — spreads each ds_read_b128 lane group
-// over four 16-B slots (guide: bank-conflict 141x down, +35%).
-DEV_INLINE unsigned swz(unsigned o) { return o ^ (((o >> 9) & 1u) << 5); }
+// ---------------------------------------------------------------------------
+// The two research variants below keep the text they had before gemm_tile.h
+// existed, and with it copies of its pieces under their old names
+// (stage_tile_glds, stage_half_glds, frag_swz, swz32, stage_k32_glds,
+// frag_k32q; swz is the header's): on the shared pieces their instruction order
+// changed and single shapes moved by +0.3 % (bk32x4) to +5 % (3-buffer) for no
+// reason found in the ISA (profiles/stage19_gemm_shared.md).  As they stand
+// their ISA is what it was.
+// ---------------------------------------------------------------------------
 
 // Stage one [256][64] bf16 tile (32 KB) into `image` via glds: 32 wave-level
 // 1-KiB pieces, 4 per wave.  The global source address carries the swizzle;
@@ -134,157 +178,9 @@ DEV_INLINE void stage_tile_glds(__bf16* image, const __hip_bfloat16* gbase,
 
 // read an A/B fragment (16x16x32 layout: lane -> row l&15, 8 k at (l>>4)*8)
 // from a swizzled [.][64] image; `row` relative to the image, k0 in [0,64)
-DEV_INLINE bf16x8_g frag_swz(const __bf16* image, int row, int k0) {
+DEV_INLINE bf16x8 frag_swz(const __bf16* image, int row, int k0) {
   const unsigned o = (unsigned)row * 128u + (unsigned)k0 * 2u;
-  return *reinterpret_cast<const bf16x8_g*>((const char*)image + swz(o));
-}
-
-__global__ __launch_bounds__(512) void fused_lora_gemm_kernel(
-    const __hip_bfloat16* __restrict__ x,   // [M,K]
-    const __hip_bfloat16* __restrict__ w,   // [N,K]
-    const __hip_bfloat16* __restrict__ t,   // [M,r] or null
-    const __hip_bfloat16* __restrict__ bw,  // [N,r] or null
-    const __hip_bfloat16* __restrict__ bias,  // [N] or null
-    __hip_bfloat16* __restrict__ y,         // [M,N]
-    long M, long N, long K, int r, float lora_scale) {
-  // one __shared__ array only (glds pipeline rule)
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  __bf16* lds = (__bf16*)smem;  // [2][A 256x64 | B 256x64] = 128 KiB
-
-  // XCD-aware blockIdx remap (guide T1, bijective form): consecutive
-  // launch ids land on the same XCD's L2 as neighbors in tile space, so
-  // the B tile reused across M-blocks stays resident (+L2 locality on
-  // the K>=2048 shapes)
-  const int nwg = gridDim.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7;
-  int wgid = blockIdx.x;
-  if (nwg >= 8) {
-    const int xcd = wgid & 7, pos = wgid >> 3;
-    wgid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + pos;
-  }
-  const int nbn = (int)(N >> 8);
-  const int bm = wgid / nbn;
-  const int bn = wgid % nbn;
-  const long m0 = (long)bm << 8;
-  const long n0 = (long)bn << 8;
-
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  const int wr = wave >> 2;   // 0..1: wave m-position
-  const int wc = wave & 3;    // 0..3: wave n-position
-  const int fr = lane & 15;   // fragment row
-  const int fq = lane >> 4;   // fragment k-quarter / C row group
-
-  f32x4_g acc[8][4];
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_g{0.f, 0.f, 0.f, 0.f};
-
-  __bf16* bufA[2] = {lds, lds + 2 * 256 * 64};
-  __bf16* bufB[2] = {lds + 256 * 64, lds + 3 * 256 * 64};
-
-  const int KT = (int)(K >> 6);
-  stage_tile_glds(bufA[0], x, m0, K, 0, wave, lane);
-  stage_tile_glds(bufB[0], w, n0, K, 0, wave, lane);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-
-  for (int kt = 0; kt < KT; ++kt) {
-    const int cur = kt & 1;
-    if (kt + 1 < KT) {
-      stage_tile_glds(bufA[cur ^ 1], x, m0, K, (kt + 1) << 6, wave, lane);
-      stage_tile_glds(bufB[cur ^ 1], w, n0, K, (kt + 1) << 6, wave, lane);
-    }
-    const __bf16* A = bufA[cur];
-    const __bf16* B = bufB[cur];
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      bf16x8_g af[8], bf[4];
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-        af[i] = frag_swz(A, wr * 128 + i * 16 + fr, ks * 32 + fq * 8);
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        bf[j] = frag_swz(B, wc * 64 + j * 16 + fr, ks * 32 + fq * 8);
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              af[i], bf[j], acc[i][j], 0, 0, 0);
-    }
-    __builtin_amdgcn_s_setprio(0);
-    // drain next tile's glds, then release the buffers we just read
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-  }
-
-  // ---- LoRA rank-r epilogue: acc += s * t-tile @ Bw-tile^T ---------------
-  if (r > 0) {
-    const int RC = r >> 6;  // [256][64] chunks per operand
-    // r<=128: both operands fit the 4 buffer slots at once
-#pragma unroll 1
-    for (int c = 0; c < RC; ++c) {
-      stage_tile_glds(bufA[c & 1], t, m0, r, c << 6, wave, lane);
-      stage_tile_glds(bufB[c & 1], bw, n0, r, c << 6, wave, lane);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      const __bf16* A = bufA[c & 1];
-      const __bf16* B = bufB[c & 1];
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        bf16x8_g af[8], bf[4];
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-          af[i] = frag_swz(A, wr * 128 + i * 16 + fr, ks * 32 + fq * 8);
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          bf[j] = frag_swz(B, wc * 64 + j * 16 + fr, ks * 32 + fq * 8);
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                af[i], bf[j], acc[i][j], 0, 0, 0);
-      }
-      __builtin_amdgcn_s_setprio(0);
-      __syncthreads();
-    }
-    // fold the LoRA scale: epilogue computed acc_main + t·Bw^T; we need
-    // acc_main + s·t·Bw^T.  Instead of scaling inside (would scale the
-    // main GEMM too), the host pre-scales t by s — nothing to do here.
-  }
-
-  // ---- epilogue: stage each wave's 128x64 tile through its LDS share ----
-  // (per-element global stores are store-issue-bound; LDS re-read gives
-  // b128 row stores — DESIGN.md rule 6)
-  __syncthreads();
-  __bf16* mine = lds + wave * (128 * 64);  // 16 KiB per wave
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int reg = 0; reg < 4; ++reg) {
-        const int row = i * 16 + fq * 4 + reg;  // within wave tile
-        const int col = j * 16 + fr;
-        float v = acc[i][j][reg];
-        if (bias) v += (float)bias[n0 + wc * 64 + col];
-        mine[row * 64 + col] = (__bf16)v;  // writes 2-way (col pairs share a
-                                           // dword), reads conflict-free b128
-      }
-  // no barrier needed: each wave reads only its own region
-#pragma unroll
-  for (int rr = 0; rr < 16; ++rr) {
-    const int row = rr * 8 + (lane >> 3);          // 0..127
-    const int cb = (lane & 7) * 8;                 // 8-col chunk
-    const bf16x8_g vv = *reinterpret_cast<const bf16x8_g*>(mine + row * 64 + cb);
-    *reinterpret_cast<bf16x8_g*>(
-        y + (m0 + wr * 128 + row) * N + n0 + wc * 64 + cb) = vv;
-  }
+  return *reinterpret_cast<const bf16x8*>((const char*)image + swz(o));
 }
 
 // ---------------------------------------------------------------------------
@@ -319,7 +215,7 @@ __global__ __launch_bounds__(512) void fused_lora_gemm3_kernel(
     const __hip_bfloat16* __restrict__ x, const __hip_bfloat16* __restrict__ w,
     const __hip_bfloat16* __restrict__ t, const __hip_bfloat16* __restrict__ bw,
     const __hip_bfloat16* __restrict__ bias, __hip_bfloat16* __restrict__ y,
-    long M, long N, long K, int r, float lora_scale) {
+    long M, long N, long K, int r) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __bf16* lds = (__bf16*)smem;  // 3 x (A 256x64 + B 128x64) = 144 KiB
 
@@ -343,11 +239,11 @@ __global__ __launch_bounds__(512) void fused_lora_gemm3_kernel(
   const int fr = lane & 15;
   const int fq = lane >> 4;
 
-  f32x4_g acc[8][2];
+  f32x4 acc[8][2];
 #pragma unroll
   for (int i = 0; i < 8; ++i)
 #pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = f32x4_g{0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   __bf16* bufA[3];
   __bf16* bufB[3];
@@ -388,7 +284,7 @@ __global__ __launch_bounds__(512) void fused_lora_gemm3_kernel(
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
-      bf16x8_g af[8], bf[2];
+      bf16x8 af[8], bf[2];
 #pragma unroll
       for (int i = 0; i < 8; ++i)
         af[i] = frag_swz(A, wr * 128 + i * 16 + fr, ks * 32 + fq * 8);
@@ -420,7 +316,7 @@ __global__ __launch_bounds__(512) void fused_lora_gemm3_kernel(
       const __bf16* B = bufB[c & 1];
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
-        bf16x8_g af[8], bf[2];
+        bf16x8 af[8], bf[2];
 #pragma unroll
         for (int i = 0; i < 8; ++i)
           af[i] = frag_swz(A, wr * 128 + i * 16 + fr, ks * 32 + fq * 8);
@@ -457,8 +353,8 @@ __global__ __launch_bounds__(512) void fused_lora_gemm3_kernel(
   for (int rr = 0; rr < 8; ++rr) {
     const int row = rr * 16 + (lane >> 2);
     const int cb = (lane & 3) * 8;
-    const bf16x8_g vv = *reinterpret_cast<const bf16x8_g*>(mine + row * 32 + cb);
-    *reinterpret_cast<bf16x8_g*>(
+    const bf16x8 vv = *reinterpret_cast<const bf16x8*>(mine + row * 32 + cb);
+    *reinterpret_cast<bf16x8*>(
         y + (m0 + wr * 128 + row) * N + n0 + wc * 32 + cb) = vv;
   }
 }
@@ -499,9 +395,9 @@ DEV_INLINE void stage_k32_glds(__bf16* image, const __hip_bfloat16* gbase,
 }
 
 // fragment at (row, k-quarter fq*8): logical byte = row*64 + fq*16
-DEV_INLINE bf16x8_g frag_k32q(const __bf16* image, int row, int fq) {
+DEV_INLINE bf16x8 frag_k32q(const __bf16* image, int row, int fq) {
   const unsigned o = (unsigned)row * 64u + (unsigned)fq * 16u;
-  return *reinterpret_cast<const bf16x8_g*>((const char*)image + swz32(o));
+  return *reinterpret_cast<const bf16x8*>((const char*)image + swz32(o));
 }
 
 __global__ __launch_bounds__(512) void fused_lora_gemm4_kernel(
@@ -530,11 +426,11 @@ __global__ __launch_bounds__(512) void fused_lora_gemm4_kernel(
   const int wr = wave >> 2, wc = wave & 3;
   const int fr = lane & 15, fq = lane >> 4;
 
-  f32x4_g acc[8][4];
+  f32x4 acc[8][4];
 #pragma unroll
   for (int i = 0; i < 8; ++i)
 #pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_g{0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   __bf16* bufA[4];
   __bf16* bufB[4];
@@ -578,7 +474,7 @@ __global__ __launch_bounds__(512) void fused_lora_gemm4_kernel(
     asm volatile("" ::: "memory");  // compiler fence: no read hoists above
     const __bf16* A = bufA[cur];
     const __bf16* B = bufB[cur];
-    bf16x8_g af[8], bf[4];
+    bf16x8 af[8], bf[4];
 #pragma unroll
     for (int i = 0; i < 8; ++i)
       af[i] = frag_k32q(A, wr * 128 + i * 16 + fr, fq);
@@ -608,7 +504,7 @@ __global__ __launch_bounds__(512) void fused_lora_gemm4_kernel(
       __syncthreads();
       const __bf16* A = bufA[c & 1];
       const __bf16* B = bufB[c & 1];
-      bf16x8_g af[8], bf[4];
+      bf16x8 af[8], bf[4];
 #pragma unroll
       for (int i = 0; i < 8; ++i)
         af[i] = frag_k32q(A, wr * 128 + i * 16 + fr, fq);
@@ -643,12 +539,11 @@ __global__ __launch_bounds__(512) void fused_lora_gemm4_kernel(
   for (int rr = 0; rr < 16; ++rr) {
     const int row = rr * 8 + (lane >> 3);
     const int cb = (lane & 7) * 8;
-    const bf16x8_g vv = *reinterpret_cast<const bf16x8_g*>(mine + row * 64 + cb);
-    *reinterpret_cast<bf16x8_g*>(
+    const bf16x8 vv = *reinterpret_cast<const bf16x8*>(mine + row * 64 + cb);
+    *reinterpret_cast<bf16x8*>(
         y + (m0 + wr * 128 + row) * N + n0 + wc * 64 + cb) = vv;
   }
 }
-
 
 // int8 variant of the dequant stage (256-element symmetric blocks,
 // scale = absmax/127 — ops/csrc/quantize.hip layout).  Requires K%256==0
@@ -669,127 +564,50 @@ DEV_INLINE void stage_tile_int8(__bf16* image, const int8_t* qdata,
   __bf16 vals[32];
 #pragma unroll
   for (int i = 0; i < 32; ++i) vals[i] = (__bf16)(pk.b[i] * sc);
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    const unsigned o = (unsigned)row * 128u + (unsigned)half * 64u + c * 16u;
-    *reinterpret_cast<bf16x8_g*>((char*)image + swz(o)) =
-        *reinterpret_cast<const bf16x8_g*>(vals + c * 8);
-  }
+  write_dequant32(image, row, half, vals);
 }
 
 __global__ __launch_bounds__(512) void fused_int8_gemm_kernel(
-    const __hip_bfloat16* __restrict__ x, const int8_t* __restrict__ qw,
-    const float* __restrict__ amax, const __hip_bfloat16* __restrict__ t,
-    const __hip_bfloat16* __restrict__ bw, const __hip_bfloat16* __restrict__ bias,
+    const __hip_bfloat16* __restrict__ x,   // [M,K]
+    const int8_t* __restrict__ qw,          // int8 codes of W [N,K]
+    const float* __restrict__ amax,         // absmax per 256-block
+    const __hip_bfloat16* __restrict__ t,   // [M,r] or null (pre-scaled)
+    const __hip_bfloat16* __restrict__ bw,  // [N,r] or null
+    const __hip_bfloat16* __restrict__ bias,
     __hip_bfloat16* __restrict__ y, long M, long N, long K, int r) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  __bf16* lds = (__bf16*)smem;
-  const int nwg = gridDim.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7;
-  int wgid = blockIdx.x;
-  if (nwg >= 8) {
-    const int xcd = wgid & 7, pos = wgid >> 3;
-    wgid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + pos;
-  }
+
+  const int wgid = xcd_remap();
   const int nbn = (int)(N >> 8);
   const long m0 = (long)(wgid / nbn) << 8;
   const long n0 = (long)(wgid % nbn) << 8;
   const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
-  const int wr = wave >> 2, wc = wave & 3;
-  const int fr = lane & 15, fq = lane >> 4;
-  f32x4_g acc[8][4];
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_g{0.f, 0.f, 0.f, 0.f};
-  __bf16* bufA[2] = {lds, lds + 2 * 256 * 64};
-  __bf16* bufB[2] = {lds + 256 * 64, lds + 3 * 256 * 64};
+  const WaveCoord wv = wave_coord();
+
+  f32x4 acc[8][4];
+  zero_acc(acc);
+
   const int KT = (int)(K >> 6);
-  stage_tile_glds(bufA[0], x, m0, K, 0, wave, lane);
-  stage_tile_int8(bufB[0], qw, amax, n0, K, 0, tid);
+  stage_glds(BUF_A(0), x, m0, K, 0, wv);
+  stage_tile_int8((__bf16*)BUF_B(0), qw, amax, n0, K, 0, tid);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
+
   for (int kt = 0; kt < KT; ++kt) {
     const int cur = kt & 1;
     if (kt + 1 < KT) {
-      stage_tile_glds(bufA[cur ^ 1], x, m0, K, (kt + 1) << 6, wave, lane);
-      stage_tile_int8(bufB[cur ^ 1], qw, amax, n0, K, (kt + 1) << 6, tid);
+      stage_glds(BUF_A(cur ^ 1), x, m0, K, (kt + 1) << 6, wv);
+      stage_tile_int8((__bf16*)BUF_B(cur ^ 1), qw, amax, n0, K, (kt + 1) << 6, tid);
     }
-    const __bf16* A = bufA[cur];
-    const __bf16* B = bufB[cur];
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      bf16x8_g af[8], bf[4];
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-        af[i] = frag_swz(A, wr * 128 + i * 16 + fr, ks * 32 + fq * 8);
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        bf[j] = frag_swz(B, wc * 64 + j * 16 + fr, ks * 32 + fq * 8);
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              af[i], bf[j], acc[i][j], 0, 0, 0);
-    }
-    __builtin_amdgcn_s_setprio(0);
+    mma_bf16_chunk(acc, BUF_A(cur), BUF_B(cur), wv);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
   }
-  if (r > 0) {
-    const int RC = r >> 6;
-#pragma unroll 1
-    for (int c = 0; c < RC; ++c) {
-      stage_tile_glds(bufA[c & 1], t, m0, r, c << 6, wave, lane);
-      stage_tile_glds(bufB[c & 1], bw, n0, r, c << 6, wave, lane);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      const __bf16* A = bufA[c & 1];
-      const __bf16* B = bufB[c & 1];
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        bf16x8_g af[8], bf[4];
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-          af[i] = frag_swz(A, wr * 128 + i * 16 + fr, ks * 32 + fq * 8);
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          bf[j] = frag_swz(B, wc * 64 + j * 16 + fr, ks * 32 + fq * 8);
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                af[i], bf[j], acc[i][j], 0, 0, 0);
-      }
-      __syncthreads();
-    }
-  }
+
+  lora_update(acc, t, bw, m0, n0, r, BUF_A(0), BUF_B(0), 2 * TILE_BYTES, wv);
+
   __syncthreads();
-  __bf16* mine = lds + wave * (128 * 64);
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int reg = 0; reg < 4; ++reg) {
-        const int row = i * 16 + fq * 4 + reg;
-        const int col = j * 16 + fr;
-        float v = acc[i][j][reg];
-        if (bias) v += (float)bias[n0 + wc * 64 + col];
-        mine[row * 64 + col] = (__bf16)v;
-      }
-#pragma unroll
-  for (int rr = 0; rr < 16; ++rr) {
-    const int row = rr * 8 + (lane >> 3);
-    const int cb = (lane & 7) * 8;
-    const bf16x8_g vv = *reinterpret_cast<const bf16x8_g*>(mine + row * 64 + cb);
-    *reinterpret_cast<bf16x8_g*>(
-        y + (m0 + wr * 128 + row) * N + n0 + wc * 64 + cb) = vv;
-  }
+  store_wave_tile((__bf16*)smem + wv.wave * (128 * 64), acc, bias, y, m0, N, n0, wv);
 }
 
 torch::Tensor fused_int8_gemm(torch::Tensor x, torch::Tensor qw, torch::Tensor amax,
@@ -802,26 +620,8 @@ torch::Tensor fused_int8_gemm(torch::Tensor x, torch::Tensor qw, torch::Tensor a
   TORCH_CHECK(M % 256 == 0 && N % 256 == 0 && K % 256 == 0,
               "fused_int8_gemm requires M%256==0, N%256==0, K%256==0");
   check_quant_w(fn, x, qw, amax, N, K, N * K, 256);
-  const int r = check_lora(fn, x, t, bw, M, N, 64, 256);
-  const bool has_lora = r > 0;
-  const __hip_bfloat16* bias_p = check_bias(fn, x, bias, N);
-  torch::Tensor t_scaled;
-  if (has_lora)
-    t_scaled = (lora_scale == 1.0) ? t : (t * lora_scale).contiguous();
-  auto y = torch::empty({M, N}, x.options());
-  auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
-  dim3 grid((M >> 8) * (N >> 8));
-  dim3 block(512);
-  size_t smem = 4 * 256 * 64 * sizeof(__bf16);
-  hipLaunchKernelGGL(fused_int8_gemm_kernel, grid, block, smem, stream,
-                     (const __hip_bfloat16*)x.data_ptr(), (const int8_t*)qw.data_ptr(),
-                     amax.data_ptr<float>(),
-                     has_lora ? (const __hip_bfloat16*)t_scaled.data_ptr() : nullptr,
-                     has_lora ? (const __hip_bfloat16*)bw.data_ptr() : nullptr,
-                     bias_p,
-                     (__hip_bfloat16*)y.data_ptr(), M, N, K, r);
-  HIP_CHECK_LAST();
-  return y;
+  return launch_fused(fn, fused_int8_gemm_kernel, x, N, 256, 4 * TILE_BYTES, 64, 256, t, bw, bias,
+                      lora_scale, (const int8_t*)qw.data_ptr(), amax.data_ptr<float>());
 }
 
 // ---------------------------------------------------------------------------
@@ -861,12 +661,7 @@ DEV_INLINE void stage_tile_nf4(__bf16* image, const uint8_t* qdata,
     vals[2 * i] = (__bf16)(NF4_CODE_G[b >> 4] * am);
     vals[2 * i + 1] = (__bf16)(NF4_CODE_G[b & 15] * am);
   }
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    const unsigned o = (unsigned)row * 128u + (unsigned)half * 64u + c * 16u;
-    *reinterpret_cast<bf16x8_g*>((char*)image + swz(o)) =
-        *reinterpret_cast<const bf16x8_g*>(vals + c * 8);
-  }
+  write_dequant32(image, row, half, vals);
 }
 
 __global__ __launch_bounds__(512) void fused_nf4_gemm_kernel(
@@ -878,126 +673,38 @@ __global__ __launch_bounds__(512) void fused_nf4_gemm_kernel(
     const __hip_bfloat16* __restrict__ bias,
     __hip_bfloat16* __restrict__ y, long M, long N, long K, int r) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  __bf16* lds = (__bf16*)smem;
 
-  const int nwg = gridDim.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7;
-  int wgid = blockIdx.x;
-  if (nwg >= 8) {
-    const int xcd = wgid & 7, pos = wgid >> 3;
-    wgid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + pos;
-  }
+  const int wgid = xcd_remap();
   const int nbn = (int)(N >> 8);
-  const int bm = wgid / nbn;
-  const int bn = wgid % nbn;
-  const long m0 = (long)bm << 8;
-  const long n0 = (long)bn << 8;
-
+  const long m0 = (long)(wgid / nbn) << 8;
+  const long n0 = (long)(wgid % nbn) << 8;
   const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
-  const int wr = wave >> 2, wc = wave & 3;
-  const int fr = lane & 15, fq = lane >> 4;
+  const WaveCoord wv = wave_coord();
 
-  f32x4_g acc[8][4];
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_g{0.f, 0.f, 0.f, 0.f};
-
-  __bf16* bufA[2] = {lds, lds + 2 * 256 * 64};
-  __bf16* bufB[2] = {lds + 256 * 64, lds + 3 * 256 * 64};
+  f32x4 acc[8][4];
+  zero_acc(acc);
 
   const int KT = (int)(K >> 6);
-  stage_tile_glds(bufA[0], x, m0, K, 0, wave, lane);
-  stage_tile_nf4(bufB[0], qw, amax, n0, K, 0, tid);
+  stage_glds(BUF_A(0), x, m0, K, 0, wv);
+  stage_tile_nf4((__bf16*)BUF_B(0), qw, amax, n0, K, 0, tid);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
   for (int kt = 0; kt < KT; ++kt) {
     const int cur = kt & 1;
     if (kt + 1 < KT) {
-      stage_tile_glds(bufA[cur ^ 1], x, m0, K, (kt + 1) << 6, wave, lane);
-      stage_tile_nf4(bufB[cur ^ 1], qw, amax, n0, K, (kt + 1) << 6, tid);
+      stage_glds(BUF_A(cur ^ 1), x, m0, K, (kt + 1) << 6, wv);
+      stage_tile_nf4((__bf16*)BUF_B(cur ^ 1), qw, amax, n0, K, (kt + 1) << 6, tid);
     }
-    const __bf16* A = bufA[cur];
-    const __bf16* B = bufB[cur];
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      bf16x8_g af[8], bf[4];
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-        af[i] = frag_swz(A, wr * 128 + i * 16 + fr, ks * 32 + fq * 8);
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        bf[j] = frag_swz(B, wc * 64 + j * 16 + fr, ks * 32 + fq * 8);
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              af[i], bf[j], acc[i][j], 0, 0, 0);
-    }
-    __builtin_amdgcn_s_setprio(0);
+    mma_bf16_chunk(acc, BUF_A(cur), BUF_B(cur), wv);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
   }
 
-  if (r > 0) {
-    const int RC = r >> 6;
-#pragma unroll 1
-    for (int c = 0; c < RC; ++c) {
-      stage_tile_glds(bufA[c & 1], t, m0, r, c << 6, wave, lane);
-      stage_tile_glds(bufB[c & 1], bw, n0, r, c << 6, wave, lane);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      const __bf16* A = bufA[c & 1];
-      const __bf16* B = bufB[c & 1];
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        bf16x8_g af[8], bf[4];
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-          af[i] = frag_swz(A, wr * 128 + i * 16 + fr, ks * 32 + fq * 8);
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          bf[j] = frag_swz(B, wc * 64 + j * 16 + fr, ks * 32 + fq * 8);
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                af[i], bf[j], acc[i][j], 0, 0, 0);
-      }
-      __builtin_amdgcn_s_setprio(0);
-      __syncthreads();
-    }
-  }
+  lora_update(acc, t, bw, m0, n0, r, BUF_A(0), BUF_B(0), 2 * TILE_BYTES, wv);
 
   __syncthreads();
-  __bf16* mine = lds + wave * (128 * 64);
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int reg = 0; reg < 4; ++reg) {
-        const int row = i * 16 + fq * 4 + reg;
-        const int col = j * 16 + fr;
-        float v = acc[i][j][reg];
-        if (bias) v += (float)bias[n0 + wc * 64 + col];
-        mine[row * 64 + col] = (__bf16)v;
-      }
-#pragma unroll
-  for (int rr = 0; rr < 16; ++rr) {
-    const int row = rr * 8 + (lane >> 3);
-    const int cb = (lane & 7) * 8;
-    const bf16x8_g vv = *reinterpret_cast<const bf16x8_g*>(mine + row * 64 + cb);
-    *reinterpret_cast<bf16x8_g*>(
-        y + (m0 + wr * 128 + row) * N + n0 + wc * 64 + cb) = vv;
-  }
+  store_wave_tile((__bf16*)smem + wv.wave * (128 * 64), acc, bias, y, m0, N, n0, wv);
 }
 
 torch::Tensor fused_nf4_gemm(torch::Tensor x, torch::Tensor qw, torch::Tensor amax,
@@ -1010,26 +717,8 @@ torch::Tensor fused_nf4_gemm(torch::Tensor x, torch::Tensor qw, torch::Tensor am
   TORCH_CHECK(M % 256 == 0 && N % 256 == 0 && K % 64 == 0,
               "fused_nf4_gemm requires M%256==0, N%256==0, K%64==0");
   check_quant_w(fn, x, qw, amax, N, K, N * K / 2, 64);
-  const int r = check_lora(fn, x, t, bw, M, N, 64, 256);
-  const bool has_lora = r > 0;
-  const __hip_bfloat16* bias_p = check_bias(fn, x, bias, N);
-  torch::Tensor t_scaled;
-  if (has_lora)
-    t_scaled = (lora_scale == 1.0) ? t : (t * lora_scale).contiguous();
-  auto y = torch::empty({M, N}, x.options());
-  auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
-  dim3 grid((M >> 8) * (N >> 8));
-  dim3 block(512);
-  size_t smem = 4 * 256 * 64 * sizeof(__bf16);
-  hipLaunchKernelGGL(fused_nf4_gemm_kernel, grid, block, smem, stream,
-                     (const __hip_bfloat16*)x.data_ptr(), qw.data_ptr<uint8_t>(),
-                     amax.data_ptr<float>(),
-                     has_lora ? (const __hip_bfloat16*)t_scaled.data_ptr() : nullptr,
-                     has_lora ? (const __hip_bfloat16*)bw.data_ptr() : nullptr,
-                     bias_p,
-                     (__hip_bfloat16*)y.data_ptr(), M, N, K, r);
-  HIP_CHECK_LAST();
-  return y;
+  return launch_fused(fn, fused_nf4_gemm_kernel, x, N, 256, 4 * TILE_BYTES, 64, 256, t, bw, bias,
+                      lora_scale, qw.data_ptr<uint8_t>(), amax.data_ptr<float>());
 }
 
 torch::Tensor fused_lora_gemm(torch::Tensor x, torch::Tensor w, torch::Tensor t,
@@ -1040,30 +729,8 @@ torch::Tensor fused_lora_gemm(torch::Tensor x, torch::Tensor w, torch::Tensor t,
   const long M = x.size(0), K = x.size(1), N = w.size(0);
   TORCH_CHECK(M % 256 == 0 && N % 256 == 0 && K % 64 == 0,
               "fused_lora_gemm requires M%256==0, N%256==0, K%64==0");
-  const int r = check_lora(fn, x, t, bw, M, N, 64, 256);
-  const bool has_lora = r > 0;
-  const __hip_bfloat16* bias_p = check_bias(fn, x, bias, N);
-  torch::Tensor t_scaled;
-  // fold the LoRA scale into t (bf16 rounding of s*t matches the
-  // composed path, which also rounds t·B^T·s contributions in bf16)
-  if (has_lora)
-    t_scaled = (lora_scale == 1.0) ? t : (t * lora_scale).contiguous();
-  auto y = torch::empty({M, N}, x.options());
-  auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
-  const int nbn = (int)(N >> 8);
-  dim3 grid((M >> 8) * nbn);
-  dim3 block(512);
-  size_t smem = 4 * 256 * 64 * sizeof(__bf16);  // 128 KiB
-  hipLaunchKernelGGL(fused_lora_gemm_kernel, grid, block, smem, stream,
-                     (const __hip_bfloat16*)x.data_ptr(),
-                     (const __hip_bfloat16*)w.data_ptr(),
-                     has_lora ? (const __hip_bfloat16*)t_scaled.data_ptr() : nullptr,
-                     has_lora ? (const __hip_bfloat16*)bw.data_ptr() : nullptr,
-                     bias_p,
-                     (__hip_bfloat16*)y.data_ptr(), M, N, K,
-                     r, (float)lora_scale);
-  HIP_CHECK_LAST();
-  return y;
+  return launch_fused(fn, fused_lora_gemm_kernel, x, N, 256, 4 * TILE_BYTES /* 128 KiB */, 64,
+                      256, t, bw, bias, lora_scale, (const __hip_bfloat16*)w.data_ptr());
 }
 
 torch::Tensor fused_lora_gemm3(torch::Tensor x, torch::Tensor w, torch::Tensor t,
@@ -1074,27 +741,9 @@ torch::Tensor fused_lora_gemm3(torch::Tensor x, torch::Tensor w, torch::Tensor t
   const long M = x.size(0), K = x.size(1), N = w.size(0);
   TORCH_CHECK(M % 256 == 0 && N % 128 == 0 && K % 64 == 0,
               "fused_lora_gemm3 requires M%256==0, N%128==0, K%64==0");
-  const int r = check_lora(fn, x, t, bw, M, N, 64, 128);
-  const bool has_lora = r > 0;
-  const __hip_bfloat16* bias_p = check_bias(fn, x, bias, N);
-  torch::Tensor t_scaled;
-  if (has_lora)
-    t_scaled = (lora_scale == 1.0) ? t : (t * lora_scale).contiguous();
-  auto y = torch::empty({M, N}, x.options());
-  auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
-  dim3 grid((M >> 8) * (N >> 7));
-  dim3 block(512);
-  size_t smem = 3 * (256 * 64 + 128 * 64) * sizeof(__bf16);  // 144 KiB
-  hipLaunchKernelGGL(fused_lora_gemm3_kernel, grid, block, smem, stream,
-                     (const __hip_bfloat16*)x.data_ptr(),
-                     (const __hip_bfloat16*)w.data_ptr(),
-                     has_lora ? (const __hip_bfloat16*)t_scaled.data_ptr() : nullptr,
-                     has_lora ? (const __hip_bfloat16*)bw.data_ptr() : nullptr,
-                     bias_p,
-                     (__hip_bfloat16*)y.data_ptr(), M, N, K,
-                     r, (float)lora_scale);
-  HIP_CHECK_LAST();
-  return y;
+  return launch_fused(fn, fused_lora_gemm3_kernel, x, N, 128,
+                      3 * (256 * 64 + 128 * 64) * sizeof(__bf16) /* 144 KiB */, 64, 128, t, bw,
+                      bias, lora_scale, (const __hip_bfloat16*)w.data_ptr());
 }
 
 torch::Tensor fused_lora_gemm4(torch::Tensor x, torch::Tensor w, torch::Tensor t,
@@ -1105,24 +754,7 @@ torch::Tensor fused_lora_gemm4(torch::Tensor x, torch::Tensor w, torch::Tensor t
   const long M = x.size(0), K = x.size(1), N = w.size(0);
   TORCH_CHECK(M % 256 == 0 && N % 256 == 0 && K % 32 == 0,
               "fused_lora_gemm4 requires M%256==0, N%256==0, K%32==0");
-  const int r = check_lora(fn, x, t, bw, M, N, 32, 256);
-  const bool has_lora = r > 0;
-  const __hip_bfloat16* bias_p = check_bias(fn, x, bias, N);
-  torch::Tensor t_scaled;
-  if (has_lora)
-    t_scaled = (lora_scale == 1.0) ? t : (t * lora_scale).contiguous();
-  auto y = torch::empty({M, N}, x.options());
-  auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
-  dim3 grid((M >> 8) * (N >> 8));
-  dim3 block(512);
-  size_t smem = 4 * 2 * 256 * 32 * sizeof(__bf16);  // 128 KiB
-  hipLaunchKernelGGL(fused_lora_gemm4_kernel, grid, block, smem, stream,
-                     (const __hip_bfloat16*)x.data_ptr(),
-                     (const __hip_bfloat16*)w.data_ptr(),
-                     has_lora ? (const __hip_bfloat16*)t_scaled.data_ptr() : nullptr,
-                     has_lora ? (const __hip_bfloat16*)bw.data_ptr() : nullptr,
-                     bias_p,
-                     (__hip_bfloat16*)y.data_ptr(), M, N, K, r);
-  HIP_CHECK_LAST();
-  return y;
+  return launch_fused(fn, fused_lora_gemm4_kernel, x, N, 256,
+                      4 * 2 * 256 * 32 * sizeof(__bf16) /* 128 KiB */, 32, 256, t, bw, bias,
+                      lora_scale, (const __hip_bfloat16*)w.data_ptr());
 }

@@ -51,11 +51,21 @@
 // Epilogue as fused_fp8_gemm: acc * xs[m]/448 (no W row scale), the rank-r
 // bf16 MFMA update on the same accumulators, bias, one rounding to bf16, b128
 // row stores through LDS (in two 64-row halves: 96 KiB hold 8 x 8 KiB).
+//
+// The device code here has copies of its own of what gemm_tile.h shares
+// between the bf16 kernels (XCD remap, coordinates, the stagers, the LoRA
+// update); only the host preparation (gemm_host.h) is shared.  Moving this
+// kernel onto shared pieces changes its instruction order, and a shift of
+// under 1 % cannot be judged with tools/bench_fp8_gemm.py, which times
+// identical code up to 1.5 % apart between two builds (the kernels timed next
+// to it differ).  fused_fp8_gemm, measured alone, did lose 1.4 % that way
+// (profiles/stage19_gemm_shared.md), so this file was left as it was.
 
 #include <ATen/hip/HIPContext.h>
 #include <torch/extension.h>
 
 #include "common.h"
+#include "gemm_host.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_m;
 typedef __attribute__((ext_vector_type(4))) float f32x4_m;
@@ -492,13 +502,6 @@ static void check_mx_u8(const char* fn, const char* what, const torch::Tensor& v
   TORCH_CHECK((uintptr_t)v.data_ptr() % 16 == 0, fn, ": ", what, " must be 16-byte aligned");
 }
 
-static void check_mx_bf16(const char* fn, const char* what, const torch::Tensor& v,
-                          const torch::Device& dev) {
-  TORCH_CHECK(v.device() == dev, fn, ": ", what, " must be on xq's device");
-  TORCH_CHECK(v.scalar_type() == torch::kBFloat16, fn, ": ", what, " must be bf16");
-  TORCH_CHECK(v.is_contiguous(), fn, ": ", what, " must be contiguous");
-}
-
 // xq / xs as quantize_rows_fp8 returns them (the kernel divides xs by 448);
 // wq / wscales as quantize_rows_mxfp4 returns them for a [N,K] weight.
 torch::Tensor fused_mxfp4_gemm(torch::Tensor xq, torch::Tensor xs, torch::Tensor wq,
@@ -520,36 +523,14 @@ torch::Tensor fused_mxfp4_gemm(torch::Tensor xq, torch::Tensor xs, torch::Tensor
   TORCH_CHECK(xs.numel() == M, fn, ": x absmax must hold one value per row");
   check_mx_u8(fn, "w codes", wq, dev, N * K / 2, "N*K/2");
   check_mx_u8(fn, "w scales", wscales, dev, N * K / MX_BLOCK, "N*K/32");
-  int r = 0;
-  torch::Tensor t_scaled;
-  if (t.defined() && t.numel() > 0) {
-    check_mx_bf16(fn, "t", t, dev);
-    TORCH_CHECK(t.dim() == 2 && t.size(0) == M, fn, ": t must be [M, r]");
-    r = (int)t.size(1);
-    TORCH_CHECK(t.size(1) % 64 == 0 && t.size(1) <= 256, fn,
-                ": r must be a multiple of 64, <= 256");
-    TORCH_CHECK(bw.defined(), fn, ": bw is required with t");
-    check_mx_bf16(fn, "bw", bw, dev);
-    TORCH_CHECK(bw.dim() == 2 && bw.size(0) == N && bw.size(1) == r, fn,
-                ": bw must be [N, r]");
-    // fold the LoRA scale into t, as the other fused GEMMs do
-    t_scaled = (lora_scale == 1.0) ? t : (t * lora_scale).contiguous();
-  }
-  const __hip_bfloat16* bias_p = nullptr;
-  if (bias.defined() && bias.numel() > 0) {
-    check_mx_bf16(fn, "bias", bias, dev);
-    TORCH_CHECK(bias.numel() == N, fn, ": bias must have N elements");
-    bias_p = (const __hip_bfloat16*)bias.data_ptr();
-  }
+  const LoraArgs a = prep_lora_bias(fn, "xq", dev, t, bw, bias, M, N, 64, 256, lora_scale);
   auto y = torch::empty({M, N}, xq.options().dtype(torch::kBFloat16));
   auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
   dim3 grid((unsigned)((M >> 8) * (N >> 8))), block(512);
   hipLaunchKernelGGL(fused_mxfp4_gemm_kernel, grid, block, MX_SMEM_BYTES, stream,
                      xq.data_ptr<uint8_t>(), xs.data_ptr<float>(), wq.data_ptr<uint8_t>(),
                      (const unsigned*)wscales.data_ptr<uint8_t>(),
-                     r > 0 ? (const __hip_bfloat16*)t_scaled.data_ptr() : nullptr,
-                     r > 0 ? (const __hip_bfloat16*)bw.data_ptr() : nullptr, bias_p,
-                     (__hip_bfloat16*)y.data_ptr(), M, N, K, r);
+                     a.t, a.bw, a.bias, (__hip_bfloat16*)y.data_ptr(), M, N, K, a.r);
   HIP_CHECK_LAST();
   return y;
 }
