@@ -125,6 +125,12 @@ torch::Tensor fused_fp8_gemm_ragged(torch::Tensor xq, torch::Tensor xs, torch::T
 std::vector<torch::Tensor> quantize_rows_fp8_scaled_padded(torch::Tensor dy, torch::Tensor ws);
 torch::Tensor fused_fp8_gemm_dx_ragged(torch::Tensor gq, torch::Tensor gs, torch::Tensor wq,
                                        long N, long K);
+std::vector<torch::Tensor> quantize_rows_fp8_padded(torch::Tensor x);
+torch::Tensor fused_fp8_gemm_kragged(torch::Tensor xq, torch::Tensor xs, torch::Tensor wq,
+                                     torch::Tensor ws, long N, long K, torch::Tensor t,
+                                     torch::Tensor bw, torch::Tensor bias, double lora_scale);
+torch::Tensor fused_fp8_gemm_dx_kragged(torch::Tensor gq, torch::Tensor gs, torch::Tensor wq,
+                                        long N, long K);
 // mxfp4_gemm.hip
 std::vector<torch::Tensor> quantize_rows_mxfp4(torch::Tensor x);
 torch::Tensor dequantize_rows_mxfp4(torch::Tensor codes, torch::Tensor scales, long R, long K,
@@ -256,6 +262,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fused_fp8_gemm_dx_ragged", &fused_fp8_gemm_dx_ragged,
         "fused_fp8_gemm_dx for any N >= 1 on the padded codes of the gradient; W rows past N "
         "are neither read nor multiplied (gfx950)",
+        py::arg("gq"), py::arg("gs"), py::arg("wq"), py::arg("N"), py::arg("K"));
+  // ragged reduction width (in_features no multiple of 128 / 256, e.g. llama_1b's down_proj
+  // at 5461): W's code rows have pitch K and come through registers
+  m.def("quantize_rows_fp8_padded", &quantize_rows_fp8_padded,
+        "quantize_rows_fp8 for any K >= 1 -> (codes uint8 [R, ceil128(K)] with zero pad bytes, "
+        "fp32 absmax [R]) (gfx950)",
+        py::arg("x"));
+  m.def("fused_fp8_gemm_kragged", &fused_fp8_gemm_kragged,
+        "fused_fp8_gemm_ragged for any K >= 1 on the padded codes of the activations; W's rows "
+        "by unaligned 16-byte loads one tile ahead, bytes past K zeroed in registers (gfx950)",
+        py::arg("xq"), py::arg("xs"), py::arg("wq"), py::arg("ws"), py::arg("N"), py::arg("K"),
+        py::arg("t"), py::arg("bw"), py::arg("bias"), py::arg("lora_scale"));
+  m.def("fused_fp8_gemm_dx_kragged", &fused_fp8_gemm_dx_kragged,
+        "fused_fp8_gemm_dx_ragged for any K >= 1: ceil(K/256) block columns, unaligned patch "
+        "loads, rows of pitch K stored up to column K (gfx950)",
         py::arg("gq"), py::arg("gs"), py::arg("wq"), py::arg("N"), py::arg("K"));
   m.def("quantize_rows_mxfp4", &quantize_rows_mxfp4,
         "bf16 [R,K] -> (e2m1 codes uint8 [R,Kp/2], E8M0 scales uint8 [R,Kp/32]), OCP MX "

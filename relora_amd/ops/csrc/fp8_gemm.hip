@@ -19,6 +19,8 @@
 //   quantize_rows_fp8    bf16 [R,K] -> (uint8 codes [R,K], fp32 absmax [R])
 //   dequantize_rows_fp8  codes, absmax -> bf16 | fp32 [R,K]
 //   fused_fp8_gemm       y = (xq·wq^T)·sx·sw^T (+bias) + s·t·Bw^T, bf16 out
+//   ..._ragged / _padded any N (out_features);  ..._kragged / quantize_rows_fp8_padded
+//                        any K (in_features) as well: W's rows through registers
 //
 // GEMM structure: the 256x256 / 8-wave / double-buffered-glds geometry of
 // fused_lora_gemm, redesigned for one-byte operands.  An LDS row stays
@@ -99,23 +101,57 @@ DEV_INLINE float group_max(float am) {
   return am;
 }
 
-template <int G, int NU>
+// Unit c of a row of any length K, for the padded form: units wholly below K
+// load two Vec8 (rows of odd K are only 2-byte aligned), the unit that
+// straddles K loads element by element behind a guard, units at or past K are
+// zeros.
+DEV_INLINE Unit16 unit_load_ragged(const __hip_bfloat16* __restrict__ xrow, int c, int K) {
+  Unit16 u;
+  if (c * 16 + 16 <= K) {
+    const Vec8<__hip_bfloat16> a = load8(xrow + c * 16), b = load8(xrow + c * 16 + 8);
+    __builtin_memcpy(&u.lo, &a, 16);
+    __builtin_memcpy(&u.hi, &b, 16);
+  } else {
+    const unsigned short* bits = reinterpret_cast<const unsigned short*>(xrow);
+    unsigned w[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int k = c * 16 + 2 * i;
+      const unsigned lo = k < K ? bits[k] : 0u, hi = k + 1 < K ? bits[k + 1] : 0u;
+      w[i] = lo | (hi << 16);
+    }
+    u.lo = make_uint4(w[0], w[1], w[2], w[3]);
+    u.hi = make_uint4(w[4], w[5], w[6], w[7]);
+  }
+  return u;
+}
+
+// PAD: any K >= 1; the code rows have pitch Kp = K rounded up to 128 and the
+// bytes [K, Kp) are zero codes, so the rows are 16-byte aligned glds sources
+// and whole 128-k tiles for fused_fp8_gemm_kernel<true, true>.
+template <int G, int NU, bool PAD>
 __global__ __launch_bounds__(256) void quantize_rows_fp8_kernel(
     const __hip_bfloat16* __restrict__ x, uint8_t* __restrict__ q,
     float* __restrict__ absmax, long R, int K) {
   const int gl = threadIdx.x & (G - 1);
   const long row = ((long)blockIdx.x * 256 + threadIdx.x) / G;
   const bool live = row < R;  // whole lane groups: shuffles stay inside a row
-  const int units = K >> 4;
+  const int Kp = PAD ? (K + 127) & ~127 : K;
+  const int units = Kp >> 4;
+  const __hip_bfloat16* xrow = x + (live ? row : 0) * K;
   const Unit16* src = reinterpret_cast<const Unit16*>(x + (live ? row : 0) * K);
-  uint4* dst = reinterpret_cast<uint4*>(q + (live ? row : 0) * K);
+  uint4* dst = reinterpret_cast<uint4*>(q + (live ? row : 0) * Kp);
   float am = 0.f;
   if (NU > 0) {
     Unit16 u[NU > 0 ? NU : 1];
 #pragma unroll
     for (int i = 0; i < NU; ++i) {
       const int c = gl + i * G;
-      u[i] = (live && c < units) ? src[c] : Unit16{make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0)};
+      if (PAD)
+        u[i] = (live && c < units) ? unit_load_ragged(xrow, c, K)
+                                   : Unit16{make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0)};
+      else
+        u[i] = (live && c < units) ? src[c] : Unit16{make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0)};
       am = fmaxf(am, unit_absmax(u[i]));
     }
     am = group_max<G>(am);
@@ -127,11 +163,13 @@ __global__ __launch_bounds__(256) void quantize_rows_fp8_kernel(
     }
   } else {
     if (live)
-      for (int c = gl; c < units; c += G) am = fmaxf(am, unit_absmax(src[c]));
+      for (int c = gl; c < units; c += G)
+        am = fmaxf(am, unit_absmax(PAD ? unit_load_ragged(xrow, c, K) : src[c]));
     am = group_max<G>(am);
     const float inv = am > 0.f ? __fdiv_rn(FP8_MAX, am) : 0.f;
     if (live)
-      for (int c = gl; c < units; c += G) dst[c] = unit_encode(src[c], inv);
+      for (int c = gl; c < units; c += G)
+        dst[c] = unit_encode(PAD ? unit_load_ragged(xrow, c, K) : src[c], inv);
   }
   if (live && gl == 0) absmax[row] = am;
 }
@@ -158,48 +196,58 @@ __global__ __launch_bounds__(256) void quantize_rows_fp8_any_kernel(
   if (lane == 0) absmax[row] = am;
 }
 
-template <int G, int NU>
+template <int G, int NU, bool PAD = false>
 static void launch_quantize(const torch::Tensor& x, torch::Tensor& q, torch::Tensor& am,
                             long R, int K, hipStream_t stream) {
   const long rows_per_block = 256 / G;
   dim3 grid((unsigned)((R + rows_per_block - 1) / rows_per_block)), block(256);
-  hipLaunchKernelGGL((quantize_rows_fp8_kernel<G, NU>), grid, block, 0, stream,
+  hipLaunchKernelGGL((quantize_rows_fp8_kernel<G, NU, PAD>), grid, block, 0, stream,
                      (const __hip_bfloat16*)x.data_ptr(), q.data_ptr<uint8_t>(),
                      am.data_ptr<float>(), R, K);
 }
 
-std::vector<torch::Tensor> quantize_rows_fp8(torch::Tensor x) {
-  const char* fn = "quantize_rows_fp8";
+template <bool PAD>
+static std::vector<torch::Tensor> quantize_rows_fp8_impl(const char* fn, torch::Tensor x) {
   TORCH_CHECK(x.is_cuda(), fn, ": x must be a GPU tensor");
   TORCH_CHECK(x.dim() == 2, fn, ": x must be 2-D [R, K]");
   TORCH_CHECK(x.is_contiguous(), fn, ": x must be contiguous");
   TORCH_CHECK(x.scalar_type() == torch::kBFloat16, fn, ": x must be bf16");
   const long R = x.size(0), K = x.size(1);
   TORCH_CHECK(R > 0 && K > 0, fn, ": R and K must be > 0");
-  TORCH_CHECK(K < (1L << 31) && R < (1L << 31) * 4, fn, ": shape too large");
-  auto q = torch::empty({R, K}, x.options().dtype(torch::kUInt8));
+  TORCH_CHECK(K < (1L << 31) - (PAD ? 128 : 0) && R < (1L << 31) * 4, fn, ": shape too large");
+  const long Kp = PAD ? (K + 127) / 128 * 128 : K;  // the form is chosen by the padded width
+  auto q = torch::empty({R, Kp}, x.options().dtype(torch::kUInt8));
   auto am = torch::empty({R}, x.options().dtype(torch::kFloat32));
   auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
   const int k = (int)K;
-  if (K % 16 != 0) {
+  if (!PAD && K % 16 != 0) {
     hipLaunchKernelGGL(quantize_rows_fp8_any_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256),
                        0, stream, (const __hip_bfloat16*)x.data_ptr(), q.data_ptr<uint8_t>(),
                        am.data_ptr<float>(), R, k);
-  } else if (K <= 256) {
-    launch_quantize<16, 1>(x, q, am, R, k, stream);
-  } else if (K <= 1024) {
-    launch_quantize<64, 1>(x, q, am, R, k, stream);
-  } else if (K <= 2048) {
-    launch_quantize<64, 2>(x, q, am, R, k, stream);
-  } else if (K <= 4096) {
-    launch_quantize<64, 4>(x, q, am, R, k, stream);
-  } else if (K <= 8192) {
-    launch_quantize<64, 8>(x, q, am, R, k, stream);
+  } else if (Kp <= 256) {
+    launch_quantize<16, 1, PAD>(x, q, am, R, k, stream);
+  } else if (Kp <= 1024) {
+    launch_quantize<64, 1, PAD>(x, q, am, R, k, stream);
+  } else if (Kp <= 2048) {
+    launch_quantize<64, 2, PAD>(x, q, am, R, k, stream);
+  } else if (Kp <= 4096) {
+    launch_quantize<64, 4, PAD>(x, q, am, R, k, stream);
+  } else if (Kp <= 8192) {
+    launch_quantize<64, 8, PAD>(x, q, am, R, k, stream);
   } else {
-    launch_quantize<64, 0>(x, q, am, R, k, stream);
+    launch_quantize<64, 0, PAD>(x, q, am, R, k, stream);
   }
   HIP_CHECK_LAST();
   return {q, am};
+}
+
+std::vector<torch::Tensor> quantize_rows_fp8(torch::Tensor x) {
+  return quantize_rows_fp8_impl<false>("quantize_rows_fp8", x);
+}
+
+// any K >= 1: codes [R, Kp], Kp = K rounded up to 128, the pad bytes zero codes
+std::vector<torch::Tensor> quantize_rows_fp8_padded(torch::Tensor x) {
+  return quantize_rows_fp8_impl<true>("quantize_rows_fp8_padded", x);
 }
 
 // ---------------------------------------------------------------------------
@@ -320,10 +368,96 @@ DEV_INLINE bf16x8_q frag_bf16(const char* image, int row, int ks, int fq) {
 #define FP8_BUF_A(b) (smem + (b) * (2 * FP8_TILE_BYTES))
 #define FP8_BUF_B(b) (smem + (b) * (2 * FP8_TILE_BYTES) + FP8_TILE_BYTES)
 
+// --- register-staged B operand for a ragged reduction width (KRAG) ----------
+// W's code rows have pitch K, any K >= 1: a row starts at any byte alignment,
+// which glds cannot source.  Each thread owns four 16-byte chunks of the
+// [256][128 B] tile: chunk c = lane&7 of rows rt + 8i, rt = wave*32 + (lane>>3).
+// A wave's load instruction covers 8 whole rows of 128 contiguous bytes with
+// unaligned 16-byte loads (one global_load_dwordx4 each); an 8-lane
+// ds_write_b128 group holds the 8 chunks of one row, which swz8 permutes
+// within the row's 128 bytes: conflict-free (tools/lds_bank_model.py
+// fp8_kragged_b_writes).
+
+DEV_INLINE i32x4_q load16_any(const char* p) {
+  i32x4_q v;
+  __builtin_memcpy(&v, p, 16);
+  return v;
+}
+
+// rows past `nrel` (the last row of W, relative to the tile) read row nrel;
+// `cb` is the lane's byte offset within a row, relative to `base`
+DEV_INLINE void load_b_rows(i32x4_q (&st)[4], const char* base, unsigned K, int rt, int nrel,
+                            unsigned cb) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int row = rt + 8 * i < nrel ? rt + 8 * i : nrel;
+    st[i] = load16_any(base + ((unsigned)row * K + cb));
+  }
+}
+
+// K < 16: a row is shorter than one chunk; bytes behind a guard, chunk 0 only
+DEV_INLINE void load_b_rows_bytes(i32x4_q (&st)[4], const char* base, unsigned K, int rt,
+                                  int nrel, int c) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int row = rt + 8 * i < nrel ? rt + 8 * i : nrel;
+    unsigned w[4] = {0u, 0u, 0u, 0u};
+    if (c == 0) {
+#pragma unroll
+      for (unsigned e = 0; e < 15; ++e)
+        if (e < K) w[e >> 2] |= (unsigned)(uint8_t)base[(unsigned)row * K + e] << (8 * (e & 3));
+    }
+    st[i] = i32x4_q{(int)w[0], (int)w[1], (int)w[2], (int)w[3]};
+  }
+}
+
+// v >> 8*s over the 16 bytes, zeros shifted in; s is wave-uniform, 1..15
+DEV_INLINE i32x4_q shr_bytes(const i32x4_q& v, int s) {
+  const unsigned w[8] = {(unsigned)v[0], (unsigned)v[1], (unsigned)v[2], (unsigned)v[3], 0u, 0u, 0u, 0u};
+  const int sd = s >> 2;
+  const unsigned sb = (unsigned)s & 3u;
+  unsigned o[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const unsigned lo = sd == 0 ? w[i] : sd == 1 ? w[i + 1] : sd == 2 ? w[i + 2] : w[i + 3];
+    const unsigned hi = sd == 0 ? w[i + 1] : sd == 1 ? w[i + 2] : sd == 2 ? w[i + 3] : w[i + 4];
+    o[i] = __builtin_amdgcn_alignbyte(hi, lo, sb);
+  }
+  return i32x4_q{(int)o[0], (int)o[1], (int)o[2], (int)o[3]};
+}
+
+// The last tile holds kv < 128 valid bytes a row.  Chunks wholly below kv load
+// as usual.  The chunk that straddles kv was loaded END-aligned (the 16 bytes
+// that end with the row, so nothing behind the row is read — for the last row
+// that would be outside wq) and is shifted down here; chunks at or past kv are
+// cleared.  Zeros, not A's zero pad, keep the bytes at k >= K out of the sums:
+// 0x7F/0xFF are NaN in e4m3 and 0 x NaN is NaN.
+DEV_INLINE void fix_b_rows_edge(i32x4_q (&st)[4], int c, int kv) {
+  const int cs = kv >> 4, rem = kv & 15;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const i32x4_q sh = shr_bytes(st[i], (16 - rem) & 15);
+    const i32x4_q z = {0, 0, 0, 0};
+    st[i] = c < cs ? st[i] : (c == cs && rem != 0) ? sh : z;
+  }
+}
+
+DEV_INLINE void write_b_rows(char* image, const i32x4_q (&st)[4], int rt, int c) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    *reinterpret_cast<i32x4_q*>(image + swz8((unsigned)(rt + 8 * i) * 128u + (unsigned)c * 16u)) =
+        st[i];
+}
+
 // RAGGED: any N >= 1.  The grid has ceil(N/256) block columns; in the last one
 // every W-side row index >= N (B tile, bw tile, wa, bias) is clamped to N-1,
 // and the epilogue stores rows of pitch N up to column N only.
-template <bool RAGGED>
+// KRAG (with RAGGED): any K >= 1 as well.  xq has pitch Kp = K rounded up to
+// 128 with zero codes in [K, Kp) (quantize_rows_fp8_padded) and comes by glds
+// as before; wq has pitch K and comes through registers (above), fetched one
+// tile ahead right after A's glds is issued, in flight during the MFMAs and
+// written to the other B image behind them.
+template <bool RAGGED, bool KRAG = false>
 __global__ __launch_bounds__(512) void fused_fp8_gemm_kernel(
     const uint8_t* __restrict__ xq,         // [M,K] e4m3 codes
     const float* __restrict__ xa,           // [M] absmax of x rows
@@ -367,18 +501,57 @@ __global__ __launch_bounds__(512) void fused_fp8_gemm_kernel(
   const char* xg = (const char*)xq;
   const char* wg = (const char*)wq;
 
-  const int KT = (int)(K >> 7);  // 128-k tiles
-  stage_tile_bytes(FP8_BUF_A(0), xg, m0, K, 0, wave, lane);
-  stage_tile_bytes<RAGGED>(FP8_BUF_B(0), wg, n0, K, 0, wave, lane, nl);
+  const long KA = KRAG ? (K + 127) & ~127L : K;  // pitch of xq, reduction depth
+  const int KT = (int)(KA >> 7);                 // 128-k tiles
+  // KRAG: this thread's chunks of every B tile, W's rows relative to row n0,
+  // valid bytes a row in the last tile
+  const int rt = wave * 32 + (lane >> 3), bc = lane & 7;
+  const int nrel = (int)(nl - n0 < 255 ? nl - n0 : 255);
+  const int kv = (int)(K - ((long)(KT - 1) << 7));
+  const char* wrow = wg + n0 * K;
+  i32x4_q st[4];
+  stage_tile_bytes(FP8_BUF_A(0), xg, m0, KA, 0, wave, lane);
+  if (KRAG) {
+    if (K < 16) {
+      load_b_rows_bytes(st, wrow, (unsigned)K, rt, nrel, bc);
+    } else if (KT == 1 && kv < 128) {
+      load_b_rows(st, wrow, (unsigned)K, rt, nrel,
+                  bc < (kv >> 4) ? (unsigned)bc * 16u : (unsigned)K - 16u);
+      fix_b_rows_edge(st, bc, kv);
+    } else {
+      load_b_rows(st, wrow, (unsigned)K, rt, nrel, (unsigned)bc * 16u);
+    }
+    write_b_rows(FP8_BUF_B(0), st, rt, bc);
+  } else {
+    stage_tile_bytes<RAGGED>(FP8_BUF_B(0), wg, n0, K, 0, wave, lane, nl);
+  }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
   for (int kt = 0; kt < KT; ++kt) {
     const int cur = kt & 1;
-    if (kt + 1 < KT) {
-      stage_tile_bytes(FP8_BUF_A(cur ^ 1), xg, m0, K, (long)(kt + 1) << 7, wave, lane);
-      stage_tile_bytes<RAGGED>(FP8_BUF_B(cur ^ 1), wg, n0, K, (long)(kt + 1) << 7, wave, lane,
-                               nl);
+    const bool more = kt + 1 < KT;
+    const bool edge = KRAG && kt + 2 == KT && kv < 128;  // uniform: next tile is short
+    if (more) {
+      stage_tile_bytes(FP8_BUF_A(cur ^ 1), xg, m0, KA, (long)(kt + 1) << 7, wave, lane);
+      if (KRAG) {
+        // the lane's row and chunk stay opaque 32-bit VGPRs next to a scalar
+        // base (saddr form): hoisted out of the loop the four offsets become
+        // 64-bit lane addresses
+        int ro = rt;
+        unsigned co = (unsigned)bc * 16u;
+        asm volatile("" : "+v"(ro), "+v"(co));
+        const unsigned k0 = (unsigned)(kt + 1) << 7;
+        if (edge) {  // K >= 128 here; full chunks as usual, the others end-aligned
+          load_b_rows(st, wrow, (unsigned)K, ro, nrel,
+                      bc < (kv >> 4) ? k0 + co : (unsigned)K - 16u);
+        } else {
+          load_b_rows(st, wrow + k0, (unsigned)K, ro, nrel, co);
+        }
+      } else {
+        stage_tile_bytes<RAGGED>(FP8_BUF_B(cur ^ 1), wg, n0, K, (long)(kt + 1) << 7, wave, lane,
+                                 nl);
+      }
     }
     const char* A = FP8_BUF_A(cur);
     const char* B = FP8_BUF_B(cur);
@@ -396,6 +569,12 @@ __global__ __launch_bounds__(512) void fused_fp8_gemm_kernel(
             af, bf[j], acc[i][j], 0 /*A e4m3*/, 0 /*B e4m3*/, 0, 0, 0, 0);
     }
     __builtin_amdgcn_s_setprio(0);
+    if (KRAG) {
+      // the other B image was last read in the previous iteration, behind its
+      // barrier; the chunk loads had the whole MFMA loop to land
+      if (edge) fix_b_rows_edge(st, bc, kv);
+      if (more) write_b_rows(FP8_BUF_B(cur ^ 1), st, rt, bc);
+    }
     // drain next tile's glds, then release the buffers we just read
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -515,16 +694,24 @@ static void check_fp8_operand(const char* fn, const char* what, const torch::Ten
 
 // xs / ws are the per-row absmax as quantize_rows_fp8 returns them; the
 // kernel turns them into scales (absmax/448) itself.
-template <bool RAGGED>
+// KRAG: xq is [M, Kp], Kp = K rounded up to 128, its pad columns zero codes
+// (the contract of quantize_rows_fp8_padded; not checked here), wq N*K bytes.
+template <bool RAGGED, bool KRAG = false>
 static torch::Tensor fused_fp8_gemm_impl(const char* fn, torch::Tensor xq, torch::Tensor xs,
-                                         torch::Tensor wq, torch::Tensor ws, long N,
+                                         torch::Tensor wq, torch::Tensor ws, long N, long K,
                                          torch::Tensor t, torch::Tensor bw, torch::Tensor bias,
                                          double lora_scale) {
   TORCH_CHECK(xq.is_cuda(), fn, ": xq must be a GPU tensor");
-  TORCH_CHECK(xq.dim() == 2, fn, ": xq must be 2-D [M, K]");
-  const long M = xq.size(0), K = xq.size(1);
+  TORCH_CHECK(xq.dim() == 2, fn, KRAG ? ": xq must be 2-D [M, Kp]" : ": xq must be 2-D [M, K]");
+  const long M = xq.size(0), KA = xq.size(1);
+  if (!KRAG) K = KA;
   TORCH_CHECK(M > 0 && K > 0 && N > 0, fn, ": M, N and K must be > 0");
-  if (RAGGED) {
+  if (KRAG) {
+    TORCH_CHECK(M % 256 == 0, fn, " requires M%256==0");
+    TORCH_CHECK(K < (1L << 24) && N < (1L << 31) && (M >> 8) * ((N + 255) >> 8) < (1L << 31), fn,
+                ": shape too large");
+    TORCH_CHECK(KA == (K + 127) / 128 * 128, fn, ": xq must have K rounded up to 128 columns");
+  } else if (RAGGED) {
     TORCH_CHECK(M % 256 == 0 && K % 128 == 0, fn, " requires M%256==0, K%128==0");
     TORCH_CHECK(N < (1L << 31) && (M >> 8) * ((N + 255) >> 8) < (1L << 31), fn,
                 ": shape too large");
@@ -533,17 +720,20 @@ static torch::Tensor fused_fp8_gemm_impl(const char* fn, torch::Tensor xq, torch
                 " requires M%256==0, N%256==0, K%128==0");
   }
   const auto dev = xq.device();
-  check_fp8_operand(fn, "x", xq, xs, dev, M, K);
+  check_fp8_operand(fn, "x", xq, xs, dev, M, KA);
   check_fp8_operand(fn, "w", wq, ws, dev, N, K);
-  if (RAGGED)  // the glds staging reads 16 bytes a lane from both code tensors
+  if (KRAG) {  // W's rows come through registers from any address
+    TORCH_CHECK((uintptr_t)xq.data_ptr() % 16 == 0, fn, ": xq must be 16-byte aligned");
+  } else if (RAGGED) {  // the glds staging reads 16 bytes a lane from both code tensors
     TORCH_CHECK((uintptr_t)xq.data_ptr() % 16 == 0 && (uintptr_t)wq.data_ptr() % 16 == 0, fn,
                 ": code tensors must be 16-byte aligned");
+  }
   const LoraArgs a = prep_lora_bias(fn, "xq", dev, t, bw, bias, M, N, 64, 256, lora_scale);
   auto y = torch::empty({M, N}, xq.options().dtype(torch::kBFloat16));
   auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
   dim3 grid((unsigned)((M >> 8) * ((RAGGED ? N + 255 : N) >> 8))), block(512);
   const size_t smem = 4 * FP8_TILE_BYTES;  // 128 KiB
-  hipLaunchKernelGGL(fused_fp8_gemm_kernel<RAGGED>, grid, block, smem, stream,
+  hipLaunchKernelGGL((fused_fp8_gemm_kernel<RAGGED, KRAG>), grid, block, smem, stream,
                      xq.data_ptr<uint8_t>(), xs.data_ptr<float>(), wq.data_ptr<uint8_t>(),
                      ws.data_ptr<float>(),
                      a.t, a.bw, a.bias, (__hip_bfloat16*)y.data_ptr(), M, N, K, a.r);
@@ -554,7 +744,7 @@ static torch::Tensor fused_fp8_gemm_impl(const char* fn, torch::Tensor xq, torch
 torch::Tensor fused_fp8_gemm(torch::Tensor xq, torch::Tensor xs, torch::Tensor wq,
                              torch::Tensor ws, long N, torch::Tensor t, torch::Tensor bw,
                              torch::Tensor bias, double lora_scale) {
-  return fused_fp8_gemm_impl<false>("fused_fp8_gemm", xq, xs, wq, ws, N, t, bw, bias,
+  return fused_fp8_gemm_impl<false>("fused_fp8_gemm", xq, xs, wq, ws, N, 0, t, bw, bias,
                                     lora_scale);
 }
 
@@ -562,8 +752,17 @@ torch::Tensor fused_fp8_gemm(torch::Tensor xq, torch::Tensor xs, torch::Tensor w
 torch::Tensor fused_fp8_gemm_ragged(torch::Tensor xq, torch::Tensor xs, torch::Tensor wq,
                                     torch::Tensor ws, long N, torch::Tensor t,
                                     torch::Tensor bw, torch::Tensor bias, double lora_scale) {
-  return fused_fp8_gemm_impl<true>("fused_fp8_gemm_ragged", xq, xs, wq, ws, N, t, bw, bias,
+  return fused_fp8_gemm_impl<true>("fused_fp8_gemm_ragged", xq, xs, wq, ws, N, 0, t, bw, bias,
                                    lora_scale);
+}
+
+// ... and for any K >= 1 (llama_1b's down_proj: K = 5461) on the padded codes
+// of the activations: xq / xs = quantize_rows_fp8_padded(x), wq [N,K] as stored
+torch::Tensor fused_fp8_gemm_kragged(torch::Tensor xq, torch::Tensor xs, torch::Tensor wq,
+                                     torch::Tensor ws, long N, long K, torch::Tensor t,
+                                     torch::Tensor bw, torch::Tensor bias, double lora_scale) {
+  return fused_fp8_gemm_impl<true, true>("fused_fp8_gemm_kragged", xq, xs, wq, ws, N, K, t, bw,
+                                         bias, lora_scale);
 }
 
 
@@ -831,9 +1030,55 @@ DEV_INLINE void zero_b_patch_edge(unsigned (&st)[16], int pc, int nv) {
     if (pc * 16 + i >= nv) st[i] = 0u;
 }
 
+// --- the patch for a ragged output width K (KRAG): W's rows have pitch K, so
+// a patch's four k bytes at n*K + 4q are an unaligned dword ------------------
+
+DEV_INLINE unsigned load32_any(const char* p) {
+  unsigned v;
+  __builtin_memcpy(&v, p, 4);
+  return v;
+}
+
+DEV_INLINE void load_b_patch_any(unsigned (&st)[16], const char* tile, long K, unsigned voff) {
+#pragma unroll
+  for (int i = 0; i < 16; ++i) st[i] = load32_any(tile + (long)i * K + voff);
+}
+
+// The last reduction tile: rows clamped as in load_b_patch_edge; `rows` points
+// at W[n_tile0][0], `koff` is the lane's byte offset within a row and `rem`
+// the bytes from `rows` to the end of wq.  The quad of W's last row that
+// straddles K would end behind wq: a dword that would, is moved back to end
+// with wq, and fix_b_patch_kedge shifts its bytes down by the difference (at
+// most 3).  Offsets are taken from rows - 4, so that they stay unsigned when
+// the tile holds fewer than 4 bytes (wq holds 4 or more).
+DEV_INLINE void load_b_patch_kedge(unsigned (&st)[16], const char* rows, unsigned K,
+                                   unsigned koff, int pc, int nv, unsigned rem) {
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const int n = pc * 16 + i;
+    const unsigned end = (unsigned)(n < nv ? n : nv - 1) * K + koff + 4u;
+    st[i] = load32_any(rows - 4 + (end < rem ? end : rem));
+  }
+}
+
+// ... and rows at or past nv are cleared, as in zero_b_patch_edge
+DEV_INLINE void fix_b_patch_kedge(unsigned (&st)[16], unsigned K, unsigned koff, int pc, int nv,
+                                  unsigned rem) {
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const int n = pc * 16 + i;
+    const unsigned end = (unsigned)(n < nv ? n : nv - 1) * K + koff + 4u;
+    st[i] = n >= nv ? 0u : st[i] >> (end > rem ? (end - rem) * 8u : 0u);
+  }
+}
+
 // RAGGED: any N >= 1.  gq has pitch Np = N rounded up to 128 with zero codes
 // in [N, Np) (quantize_rows_fp8_scaled_padded), wq holds N rows.
-template <bool RAGGED>
+// KRAG (with RAGGED): any K >= 1 as well; ceil(K/256) block columns.  In the
+// edge column the patches with 4q at or past K are clamped to the last valid
+// quad (their columns are never stored), and the bytes that the straddling
+// quad picks up from the next row of W only feed columns nobody stores.
+template <bool RAGGED, bool KRAG = false>
 __global__ __launch_bounds__(512) void fused_fp8_gemm_dx_kernel(
     const uint8_t* __restrict__ gq,    // [M,N] e4m3 codes of dy*diag(sw)
     const float* __restrict__ ga,      // [M] absmax of its rows
@@ -851,7 +1096,7 @@ __global__ __launch_bounds__(512) void fused_fp8_gemm_dx_kernel(
     const int xcd = wgid & 7, pos = wgid >> 3;
     wgid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + pos;
   }
-  const int nbk = (int)(K >> 8);
+  const int nbk = (int)((KRAG ? K + 255 : K) >> 8);
   const long m0 = (long)(wgid / nbk) << 8;
   const long k0 = (long)(wgid % nbk) << 8;
 
@@ -865,7 +1110,11 @@ __global__ __launch_bounds__(512) void fused_fp8_gemm_dx_kernel(
   // this thread's patch of every W tile
   const int pq = (lane & 3) | ((lane >> 3) << 2) | ((wave & 1) << 5);
   const int pc = (wave >> 1) * 2 + ((lane >> 2) & 1);
-  const unsigned voff = (unsigned)(pc * 16) * (unsigned)K + (unsigned)(pq * 4);
+  // KRAG: kw columns of this block are below K; the lane's quad clamped to the
+  // last one that starts below K
+  const int kw = (int)(K - k0 < 256 ? K - k0 : 256);
+  const int qo = KRAG ? (pq * 4 < ((kw - 1) & ~3) ? pq * 4 : (kw - 1) & ~3) : pq * 4;
+  const unsigned voff = (unsigned)(pc * 16) * (unsigned)K + (unsigned)qo;
 
   f32x4_q acc[8][4];
 #pragma unroll
@@ -881,8 +1130,24 @@ __global__ __launch_bounds__(512) void fused_fp8_gemm_dx_kernel(
   const int NT = (int)(ND >> 7);                   // 128-n tiles
   // rows of W in the last tile; < 128 only when RAGGED
   const int nv = RAGGED ? (int)(N - ((long)(NT - 1) << 7)) : 128;
+  // KRAG: the last tile takes the edge path when it is short or a quad
+  // straddles K; with K < 4 every dword spans rows, so every tile takes it
+  const bool kedge = KRAG && (nv < 128 || (K & 3) != 0);
+  auto kedge_rem = [&](int nt_) {  // bytes from the tile's first row to the end of wq
+    long l = (N - ((long)nt_ << 7)) * K;
+    if (nt_ == 0 && l < 4) l = 4;  // N*K < 4: the host has padded wq to four bytes
+    return (unsigned)(l < 0xffffffffL ? l : 0xffffffffL);
+  };
   stage_tile_bytes(FP8_BUF_A(0), gg, m0, ND, 0, wave, lane);
-  if (RAGGED && NT == 1 && nv < 128) {
+  if (KRAG) {
+    if ((NT == 1 && kedge) || K < 4) {
+      const int nvt = NT == 1 ? nv : 128;
+      load_b_patch_kedge(st, (const char*)wq, (unsigned)K, (unsigned)k0 + qo, pc, nvt, kedge_rem(0));
+      fix_b_patch_kedge(st, (unsigned)K, (unsigned)k0 + qo, pc, nvt, kedge_rem(0));
+    } else {
+      load_b_patch_any(st, wg, K, voff);
+    }
+  } else if (RAGGED && NT == 1 && nv < 128) {
     load_b_patch_edge(st, wg, (unsigned)K, pq, pc, nv);
     zero_b_patch_edge(st, pc, nv);
   } else {
@@ -895,11 +1160,24 @@ __global__ __launch_bounds__(512) void fused_fp8_gemm_dx_kernel(
   for (int nt = 0; nt < NT; ++nt) {
     const int cur = nt & 1;
     const bool more = nt + 1 < NT;
-    const bool edge = RAGGED && nt + 2 == NT && nv < 128;  // uniform: next tile is short
+    // uniform: the next tile is short (KRAG: or has a quad that straddles K)
+    const bool edge = RAGGED && ((nt + 2 == NT && (KRAG ? kedge : nv < 128)) || (KRAG && K < 4));
+    const int nvt = nt + 2 == NT ? nv : 128;  // KRAG: rows of the next tile
     if (more) {
       stage_tile_bytes(FP8_BUF_A(cur ^ 1), gg, m0, ND, (long)(nt + 1) << 7, wave, lane);
       const char* tile = wg + ((long)(nt + 1) << 7) * K;
-      if (edge) {
+      if (KRAG) {
+        // opaque, as below: only the quad and the chunk stay live across the
+        // MFMAs, the offsets are rebuilt from them for every tile
+        int qv = qo, co = pc;
+        asm volatile("" : "+v"(qv), "+v"(co));
+        if (edge) {
+          load_b_patch_kedge(st, tile - k0, (unsigned)K, (unsigned)k0 + qv, co, nvt,
+                             kedge_rem(nt + 1));
+        } else {
+          load_b_patch_any(st, tile, K, (unsigned)(co * 16) * (unsigned)K + (unsigned)qv);
+        }
+      } else if (edge) {
         int q4 = pq;  // opaque like vo below, so the 16 offsets are not hoisted
         asm volatile("" : "+v"(q4));
         load_b_patch_edge(st, tile, (unsigned)K, q4, pc, nv);
@@ -929,7 +1207,15 @@ __global__ __launch_bounds__(512) void fused_fp8_gemm_dx_kernel(
     __builtin_amdgcn_s_setprio(0);
     // the other B image was last read in the previous iteration, behind its
     // barrier; the patch loads had the whole MFMA loop to land
-    if (edge) zero_b_patch_edge(st, pc, nv);
+    if (KRAG) {
+      if (edge && more) {
+        int qv = qo, co = pc;
+        asm volatile("" : "+v"(qv), "+v"(co));
+        fix_b_patch_kedge(st, (unsigned)K, (unsigned)k0 + qv, co, nvt, kedge_rem(nt + 1));
+      }
+    } else if (edge) {
+      zero_b_patch_edge(st, pc, nv);
+    }
     if (more) write_b_patch(FP8_BUF_B(cur ^ 1), st, pq, pc);
     // drain next tile's glds, then release the buffers we just read
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -959,12 +1245,27 @@ __global__ __launch_bounds__(512) void fused_fp8_gemm_dx_kernel(
     const int row = rr * 8 + (lane >> 3);          // 0..127
     const int cb = (lane & 7) * 8;                 // 8-col chunk
     const bf16x8_q vv = *reinterpret_cast<const bf16x8_q*>(mine + row * 64 + cb);
-    *reinterpret_cast<bf16x8_q*>(dx + (m0 + wr * 128 + row) * K + k0 + wc * 64 + cb) = vv;
+    if (KRAG) {
+      // the ragged store path of fused_fp8_gemm_kernel, pitch K
+      const long col = k0 + wc * 64 + cb;
+      __hip_bfloat16* dst = dx + (m0 + wr * 128 + row) * K + col;
+      if (col + 8 <= K) {
+        store8(dst, *reinterpret_cast<const Vec8<__hip_bfloat16>*>(&vv));
+      } else {
+        const __hip_bfloat16* sv = reinterpret_cast<const __hip_bfloat16*>(&vv);
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+          if (col + e < K) dst[e] = sv[e];
+      }
+    } else {
+      *reinterpret_cast<bf16x8_q*>(dx + (m0 + wr * 128 + row) * K + k0 + wc * 64 + cb) = vv;
+    }
   }
 }
 
 // N: rows of W.  Aligned: gq is [M,N].  RAGGED: gq is [M,Np], Np = N rounded up to 128.
-template <bool RAGGED>
+// KRAG: any K >= 1 as well, wq from any address.
+template <bool RAGGED, bool KRAG = false>
 static torch::Tensor fused_fp8_gemm_dx_impl(const char* fn, torch::Tensor gq, torch::Tensor gs,
                                             torch::Tensor wq, long N, long K) {
   TORCH_CHECK(gq.is_cuda(), fn, ": gq must be a GPU tensor");
@@ -973,14 +1274,16 @@ static torch::Tensor fused_fp8_gemm_dx_impl(const char* fn, torch::Tensor gq, to
   if (!RAGGED) N = ND;
   TORCH_CHECK(M > 0 && N > 0 && K > 0, fn, ": M, N and K must be > 0");
   if (RAGGED) {
-    TORCH_CHECK(M % 256 == 0 && K % 256 == 0, fn, " requires M%256==0, K%256==0");
+    TORCH_CHECK(M % 256 == 0 && (KRAG || K % 256 == 0), fn,
+                KRAG ? " requires M%256==0" : " requires M%256==0, K%256==0");
     TORCH_CHECK(N < (1L << 31) - 128, fn, ": shape too large");
     TORCH_CHECK(ND == (N + 127) / 128 * 128, fn, ": gq must have N rounded up to 128 columns");
   } else {
     TORCH_CHECK(M % 256 == 0 && K % 256 == 0 && N % 128 == 0, fn,
                 " requires M%256==0, K%256==0, N%128==0");
   }
-  TORCH_CHECK(K < (1L << 24) && N < (1L << 31) && (M >> 8) * (K >> 8) < (1L << 31), fn,
+  const long nbk = (KRAG ? K + 255 : K) >> 8;
+  TORCH_CHECK(K < (1L << 24) && N < (1L << 31) && (M >> 8) * nbk < (1L << 31), fn,
               ": shape too large");
   const auto dev = gq.device();
   check_fp8_operand(fn, "g", gq, gs, dev, M, ND);
@@ -988,13 +1291,16 @@ static torch::Tensor fused_fp8_gemm_dx_impl(const char* fn, torch::Tensor gq, to
   TORCH_CHECK(wq.scalar_type() == torch::kUInt8, fn, ": w codes must be uint8");
   TORCH_CHECK(wq.is_contiguous(), fn, ": w codes must be contiguous");
   TORCH_CHECK(wq.numel() == N * K, fn, ": w codes must hold N*K values");
-  TORCH_CHECK((uintptr_t)gq.data_ptr() % 16 == 0 && (uintptr_t)wq.data_ptr() % 16 == 0, fn,
-              ": code tensors must be 16-byte aligned");
+  if (KRAG && N * K < 4)  // the patches are dword loads: give the kernel four bytes to read
+    wq = torch::cat({wq.flatten(), torch::zeros({4 - N * K}, wq.options())});
+  // KRAG: W's patches are unaligned dwords whatever wq's address
+  TORCH_CHECK((uintptr_t)gq.data_ptr() % 16 == 0 && (KRAG || (uintptr_t)wq.data_ptr() % 16 == 0),
+              fn, KRAG ? ": gq must be 16-byte aligned" : ": code tensors must be 16-byte aligned");
   auto dx = torch::empty({M, K}, gq.options().dtype(torch::kBFloat16));
   auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
-  dim3 grid((unsigned)((M >> 8) * (K >> 8))), block(512);
+  dim3 grid((unsigned)((M >> 8) * nbk)), block(512);
   const size_t smem = 4 * FP8_TILE_BYTES;  // 128 KiB
-  hipLaunchKernelGGL(fused_fp8_gemm_dx_kernel<RAGGED>, grid, block, smem, stream,
+  hipLaunchKernelGGL((fused_fp8_gemm_dx_kernel<RAGGED, KRAG>), grid, block, smem, stream,
                      gq.data_ptr<uint8_t>(), gs.data_ptr<float>(), wq.data_ptr<uint8_t>(),
                      (__hip_bfloat16*)dx.data_ptr(), M, N, K);
   HIP_CHECK_LAST();
@@ -1010,6 +1316,12 @@ torch::Tensor fused_fp8_gemm_dx(torch::Tensor gq, torch::Tensor gs, torch::Tenso
 torch::Tensor fused_fp8_gemm_dx_ragged(torch::Tensor gq, torch::Tensor gs, torch::Tensor wq,
                                        long N, long K) {
   return fused_fp8_gemm_dx_impl<true>("fused_fp8_gemm_dx_ragged", gq, gs, wq, N, K);
+}
+
+// ... and for any K >= 1 (llama_1b's down_proj: dx is [M, 5461]); dx has pitch K
+torch::Tensor fused_fp8_gemm_dx_kragged(torch::Tensor gq, torch::Tensor gs, torch::Tensor wq,
+                                        long N, long K) {
+  return fused_fp8_gemm_dx_impl<true, true>("fused_fp8_gemm_dx_kragged", gq, gs, wq, N, K);
 }
 
 #if defined(__HIP_DEVICE_COMPILE__)

@@ -810,10 +810,15 @@ class _FusedLoRALinear(torch.autograd.Function):
 
 
 # fp8 frozen W whose out_features is no multiple of 256 (forward) / 128 (dx),
-# e.g. llama_1b's gate/up at 5461: the ragged variants of the fp8 GEMMs
-# (ops/csrc/fp8_gemm.hip).  RELORA_AMD_FP8_RAGGED=0 sends those shapes back to
-# the materialize arm.
+# e.g. llama_1b's gate/up at 5461, or whose in_features is no multiple of 128
+# (forward) / 256 (dx), e.g. its down_proj: the ragged variants of the fp8
+# GEMMs (ops/csrc/fp8_gemm.hip).  RELORA_AMD_FP8_RAGGED=0 sends those shapes
+# back to the materialize arm.
 _FP8_RAGGED = os.environ.get("RELORA_AMD_FP8_RAGGED", "1") != "0"
+# the two directions of the ragged reduction width, each dispatched where its
+# measured A/B favours it (docs/KERNELS.md "Ragged reduction width")
+_FP8_KRAGGED_FWD = True
+_FP8_KRAGGED_DX = True
 
 
 class _QuantizedLoRALinear(torch.autograd.Function):
@@ -865,6 +870,15 @@ class _QuantizedLoRALinear(torch.autograd.Function):
             xq, xs = hip.ext().quantize_rows_fp8(x2d)
             y = hip.ext().fused_fp8_gemm(
                 xq, xs, qw.qdata, qw.absmax, N, t_u, lora_B,
+                bias if bias is not None else empty, scale)
+            del xq, xs
+        elif (_FP8_RAGGED and _FP8_KRAGGED_FWD and qw.mode == "fp8" and M % 256 == 0
+              and K % 128 != 0 and r % 64 == 0 and r <= 256 and _FUSED_K1 != "0"):
+            # ragged reduction width, any N: activation codes padded with zero
+            # codes to whole 128-k tiles, W's rows of pitch K through registers
+            xq, xs = hip.ext().quantize_rows_fp8_padded(x2d)
+            y = hip.ext().fused_fp8_gemm_kragged(
+                xq, xs, qw.qdata, qw.absmax, N, K, t_u, lora_B,
                 bias if bias is not None else empty, scale)
             del xq, xs
         elif aligned and qw.mode == "mxfp4" and K % 128 == 0 and K <= 8192:
@@ -922,6 +936,13 @@ class _QuantizedLoRALinear(torch.autograd.Function):
             # reduction tiles, W's missing rows zeroed in registers
             gq, gs = hip.ext().quantize_rows_fp8_scaled_padded(dy2d, qw.absmax)
             dx = hip.ext().fused_fp8_gemm_dx_ragged(gq, gs, qw.qdata, N, K)
+            del gq, gs
+        elif (ctx.fp8_backward and _FP8_RAGGED and _FP8_KRAGGED_DX and qw.mode == "fp8"
+                and M % 256 == 0 and K % 256 != 0 and _FUSED_K1 != "0"):
+            # ragged output width of dx, any N: ceil(K/256) block columns,
+            # W's patches as unaligned dwords
+            gq, gs = hip.ext().quantize_rows_fp8_scaled_padded(dy2d, qw.absmax)
+            dx = hip.ext().fused_fp8_gemm_dx_kragged(gq, gs, qw.qdata, N, K)
             del gq, gs
         else:
             w = qw.materialize(torch.bfloat16)  # transient dense W for dX only

@@ -422,3 +422,46 @@ if __name__ == "__main__":
     for name, fn in (("kernel", fp8_dx_patch), ("naive", fp8_dx_patch_naive)):
         ok, ways = verify(fp8_dx_patch_writes(fn), "write_b128")
         print(f"fp8_gemm_dx patch writes, {name}: {'conflict-free' if ok else f'{ways}-way'}")
+
+
+# ---------------------------------------------------------------------------
+# fused_fp8_gemm_kragged (fp8_gemm.hip): the B image [256 n][128 B] is written
+# from registers, row-major like the glds image.  A thread owns chunk c of
+# rows rt + 8i (i = 0..3); its four b128 stores go to fp8_gemm_swz(row*128 +
+# c*16), which fp8_gemm_frag_reads reads unchanged.
+# ---------------------------------------------------------------------------
+
+def fp8_kragged_chunk(wave, lane):
+    """the kernel's assignment -> (first row rt, chunk c): a wave instruction
+    covers 8 whole rows, an 8-lane write group one row's 8 chunks."""
+    return wave * 32 + (lane >> 3), lane & 7
+
+
+def fp8_kragged_chunk_colwise(wave, lane):
+    """lane l -> row l of a 64-row band, one chunk column per instruction:
+    contiguous in neither memory nor banks."""
+    return wave * 32 + (lane & 7), lane >> 3
+
+
+def fp8_kragged_b_writes(assign=fp8_kragged_chunk):
+    """every b128 write of one B image: (wave, i)."""
+    for wave in range(8):
+        for i in range(4):
+            addrs = {}
+            for lane in range(64):
+                rt, c = assign(wave, lane)
+                addrs[lane] = fp8_gemm_swz((rt + 8 * i) * 128 + c * 16)
+            yield addrs
+
+
+def fp8_kragged_cover(assign=fp8_kragged_chunk):
+    """the (row, chunk) pairs of all 512 threads x 4: must be all 256 x 8, once each."""
+    return sorted((assign(w, l)[0] + 8 * i, assign(w, l)[1])
+                  for w in range(8) for l in range(64) for i in range(4))
+
+
+if __name__ == "__main__":
+    for name, fn in (("kernel", fp8_kragged_chunk), ("column-wise", fp8_kragged_chunk_colwise)):
+        ok, ways = verify(fp8_kragged_b_writes(fn), "write_b128")
+        print(f"fp8_gemm_kragged B chunk writes, {name}: {'conflict-free' if ok else f'{ways}-way'}")
+    assert fp8_kragged_cover() == [(r, c) for r in range(256) for c in range(8)]
