@@ -138,6 +138,9 @@ torch::Tensor dequantize_rows_mxfp4(torch::Tensor codes, torch::Tensor scales, l
 torch::Tensor fused_mxfp4_gemm(torch::Tensor xq, torch::Tensor xs, torch::Tensor wq,
                                torch::Tensor wscales, long N, torch::Tensor t,
                                torch::Tensor bw, torch::Tensor bias, double lora_scale);
+torch::Tensor fused_mxfp4_gemm_ragged(torch::Tensor xq, torch::Tensor xs, torch::Tensor wq,
+                                      torch::Tensor wscales, long N, long K, torch::Tensor t,
+                                      torch::Tensor bw, torch::Tensor bias, double lora_scale);
 // attention.hip
 std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor v,
                                     double scale, c10::optional<torch::Tensor> doc_start);
@@ -289,6 +292,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "256^2 glds tile (gfx950)",
         py::arg("xq"), py::arg("xs"), py::arg("wq"), py::arg("wscales"), py::arg("N"),
         py::arg("t"), py::arg("bw"), py::arg("bias"), py::arg("lora_scale"));
+  // any N and K (llama_1b's MLP at 5461); xq / xs: quantize_rows_fp8_padded when K % 128 != 0
+  m.def("fused_mxfp4_gemm_ragged", &fused_mxfp4_gemm_ragged,
+        "fused_mxfp4_gemm for any N >= 1 and K >= 1: clamped edge block column and odd-pitch row "
+        "stores; W's code rows of pitch Kp/2 by glds, scale dwords from any byte address, the "
+        "missing blocks of a row's last tile clamped and scaled by 2^0 (gfx950)",
+        py::arg("xq"), py::arg("xs"), py::arg("wq"), py::arg("wscales"), py::arg("N"),
+        py::arg("K"), py::arg("t"), py::arg("bw"), py::arg("bias"), py::arg("lora_scale"));
   // doc_start: optional int32 [B, S] intra-document mask (padded head_dim <= 64)
   m.def("attn_fwd", &attn_fwd, "causal flash attention forward (gfx950 MFMA)",
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("scale"),

@@ -24,6 +24,8 @@
 //   dequantize_rows_mxfp4  codes, scales -> bf16 | fp32 [R,K]
 //   fused_mxfp4_gemm       y = (xq·W4^T)·sx (+bias) + s·t·Bw^T, bf16 out,
 //                          xq/xs from quantize_rows_fp8, W4 as stored
+//   ..._ragged             any N (out_features) and any K (in_features): xq/xs
+//                          from quantize_rows_fp8_padded when K % 128 != 0
 //
 // GEMM structure: fused_fp8_gemm's 256x256 tile, 8 waves (2M x 4N),
 // double-buffered global_load_lds staging, XCD remap and one vmcnt(0) +
@@ -273,13 +275,19 @@ DEV_INLINE unsigned swz_b(unsigned o) { return o ^ (((o >> 9) & 1u) << 5); }
 // Stage one [256][128 B] tile (32 KiB) via glds: 32 wave-level 1-KiB pieces
 // (8 full rows each), 4 per wave.  The LDS image is lane-linear as glds
 // requires; the per-lane GLOBAL source address carries the swizzle.
+// CLAMP: rows past `last` read row `last` instead (the edge tile of a ragged
+// operand: nothing outside the allocation is touched, the image rows feed
+// accumulators nobody stores).
+template <bool CLAMP = false>
 DEV_INLINE void stage_a_tile(char* image, const char* gbase, long row0, long ld, long k0,
-                             int wave, int lane) {
+                             int wave, int lane, long last = 0) {
 #pragma unroll
   for (int p4 = 0; p4 < 4; ++p4) {
     const int piece = wave * 4 + p4;
     const unsigned s = swz_a(piece * 1024u + lane * 16u);  // source byte in tile
-    const char* src = gbase + (row0 + (s >> 7)) * ld + k0 + (s & 127u);
+    long row = row0 + (s >> 7);
+    if (CLAMP) row = row < last ? row : last;
+    const char* src = gbase + row * ld + k0 + (s & 127u);
     __builtin_amdgcn_global_load_lds(
         (const __attribute__((address_space(1))) unsigned int*)src,
         (__attribute__((address_space(3))) unsigned int*)(image) + (piece * 1024u) / 4,
@@ -300,6 +308,39 @@ DEV_INLINE void stage_b_tile(char* image, const char* gbase, long row0, long ld,
         (__attribute__((address_space(3))) unsigned int*)(image) + (piece * 1024u) / 4,
         16, 0, 0);
   }
+}
+
+// The same for a ragged W: rows past `last` read row `last`; with KRAG a row
+// of the tile holds only `nbt` 16-byte chunks (the MX blocks that exist in the
+// last 128-k tile of a row of pitch Kp/2), and a lane whose swizzled source
+// chunk lies behind them reads the row's last existing chunk instead.  Those
+// codes are finite (e2m1 has no NaN), get the scale byte 127 and meet the zero
+// codes of xq's pad.  Rows of pitch Kp/2 are multiples of 16 bytes, so glds
+// sources them at any K.
+template <bool KRAG>
+DEV_INLINE void stage_b_tile_edge(char* image, const char* gbase, long row0, long ld, long k0,
+                                  int wave, int lane, long last, int nbt) {
+#pragma unroll
+  for (int p2 = 0; p2 < 2; ++p2) {
+    const int piece = wave * 2 + p2;
+    const unsigned s = swz_b(piece * 1024u + lane * 16u);
+    long row = row0 + (s >> 6);
+    row = row < last ? row : last;
+    unsigned col = s & 63u;
+    if (KRAG) col = min(col, (unsigned)(nbt - 1) * 16u);
+    const char* src = gbase + row * ld + k0 + col;
+    __builtin_amdgcn_global_load_lds(
+        (const __attribute__((address_space(1))) unsigned int*)src,
+        (__attribute__((address_space(3))) unsigned int*)(image) + (piece * 1024u) / 4,
+        16, 0, 0);
+  }
+}
+
+// a dword of scale bytes from any byte address (global memory takes it)
+DEV_INLINE unsigned load_u32_any(const char* p) {
+  unsigned v;
+  __builtin_memcpy(&v, p, 4);
+  return v;
 }
 
 // e4m3 A fragment: k = 16*fq .. +15 and 64+16*fq .. +15 of `row` (chunks fq, 4+fq)
@@ -327,11 +368,25 @@ DEV_INLINE bf16x8_m frag_bf16_a(const char* image, int row, int ks, int fq) {
 #define MX_BUF_B(b) (smem + (b) * (MX_A_BYTES + MX_B_BYTES) + MX_A_BYTES)
 #define MX_SMEM_BYTES (2 * (MX_A_BYTES + MX_B_BYTES))  // 96 KiB
 
+// RAGGED: any N >= 1.  The grid has ceil(N/256) block columns; in the last one
+// every W-side row index >= N (B tile, bw tile, scale row, bias) is clamped to
+// N-1, and the epilogue stores rows of pitch N up to column N only.  The scale
+// dwords are addressed by byte (base + 32-bit lane offset) and may be unaligned.
+// KRAG (with RAGGED): any K >= 1 as well.  xq has pitch Kp128 = K rounded up to
+// 128 with zero codes in [K, Kp128) (quantize_rows_fp8_padded); wq has pitch
+// Kp/2 and wsc bpr = ceil(K/32) bytes a row, Kp = K rounded up to 32.  The last
+// tile of a row holds nb = bpr - 4*(KT-1) blocks (1..4): its code chunks past
+// nb are clamped in stage_b_tile_edge, its scale dword is loaded END-aligned
+// (the four bytes that end with the row, so nothing behind the row, for the
+// last row nothing behind wsc, is read), shifted down, and the bytes of the
+// missing blocks are set to 127: 0xFF is NaN in E8M0 and must not reach the
+// matrix instruction.  A row shorter than a dword (K <= 96) loads byte by byte.
+template <bool RAGGED, bool KRAG>
 __global__ __launch_bounds__(512) void fused_mxfp4_gemm_kernel(
-    const uint8_t* __restrict__ xq,         // [M,K] e4m3 codes
+    const uint8_t* __restrict__ xq,         // [M,K] e4m3 codes ([M,Kp128] with KRAG)
     const float* __restrict__ xa,           // [M] absmax of x rows
-    const uint8_t* __restrict__ wq,         // [N,K/2] e2m1 codes
-    const unsigned* __restrict__ wsc,       // [N,K/128] dwords of 4 E8M0 bytes
+    const uint8_t* __restrict__ wq,         // [N,K/2] e2m1 codes ([N,Kp/2] with KRAG)
+    const unsigned* __restrict__ wsc,       // [N,K/128] dwords of 4 E8M0 bytes ([N,bpr] bytes)
     const __hip_bfloat16* __restrict__ t,   // [M,r] or null (pre-scaled)
     const __hip_bfloat16* __restrict__ bw,  // [N,r] or null
     const __hip_bfloat16* __restrict__ bias,  // [N] or null
@@ -348,9 +403,10 @@ __global__ __launch_bounds__(512) void fused_mxfp4_gemm_kernel(
     const int xcd = wgid & 7, pos = wgid >> 3;
     wgid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + pos;
   }
-  const int nbn = (int)(N >> 8);
+  const int nbn = (int)((RAGGED ? N + 255 : N) >> 8);
   const long m0 = (long)(wgid / nbn) << 8;
   const long n0 = (long)(wgid % nbn) << 8;
+  const long nl = N - 1;  // last row of W (RAGGED clamps to it)
 
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -367,27 +423,72 @@ __global__ __launch_bounds__(512) void fused_mxfp4_gemm_kernel(
 
   const char* xg = (const char*)xq;
   const char* wg = (const char*)wq;
-  const long ldw = K >> 1;          // W row pitch in bytes
-  const int KT = (int)(K >> 7);     // 128-k tiles = scale dwords per W row
+  const long KA = KRAG ? (K + 127) & ~127L : K;         // pitch of xq, reduction depth
+  const int bpr = (int)(KRAG ? (K + 31) >> 5 : K >> 5);  // scale bytes per W row
+  const long ldw = KRAG ? (long)bpr * 16 : K >> 1;       // W row pitch in bytes
+  const int KT = (int)(KA >> 7);     // 128-k tiles (= scale dwords per W row unless KRAG)
+  const int nb = KRAG ? bpr - 4 * (KT - 1) : 4;          // blocks in a row's last tile
   // this lane's 4 scale rows (one per column fragment), tile 0
   const unsigned* srow = wsc + (n0 + wc * 64 + fr) * KT;
+  // RAGGED: byte offsets of the (clamped) rows from row n0, 32-bit next to a
+  // scalar base
+  const char* sbase = (const char*)wsc + n0 * bpr;
+  unsigned so[4];
   unsigned sc[4];
+  if (RAGGED) {
+    const int nrel = (int)(nl - n0 < 255 ? nl - n0 : 255);
 #pragma unroll
-  for (int j = 0; j < 4; ++j) sc[j] = srow[(long)j * 16 * KT];
+    for (int j = 0; j < 4; ++j) so[j] = (unsigned)min(wc * 64 + j * 16 + fr, nrel) * (unsigned)bpr;
+    if (KRAG && bpr < 4) {  // K <= 96: one tile, the row is shorter than a dword
+      const unsigned fill = 0x7f7f7f7fu << (8 * bpr);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        unsigned w = fill;
+#pragma unroll
+        for (int e = 0; e < 3; ++e)
+          if (e < bpr) w |= (unsigned)(uint8_t)sbase[so[j] + e] << (8 * e);
+        sc[j] = w;
+      }
+    } else {  // tile 0 is whole, or the only one with bpr == 4
+#pragma unroll
+      for (int j = 0; j < 4; ++j) sc[j] = load_u32_any(sbase + so[j]);
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) sc[j] = srow[(long)j * 16 * KT];
+  }
 
-  stage_a_tile(MX_BUF_A(0), xg, m0, K, 0, wave, lane);
-  stage_b_tile(MX_BUF_B(0), wg, n0, ldw, 0, wave, lane);
+  stage_a_tile(MX_BUF_A(0), xg, m0, KA, 0, wave, lane);
+  if (RAGGED)
+    stage_b_tile_edge<KRAG>(MX_BUF_B(0), wg, n0, ldw, 0, wave, lane, nl, KT == 1 ? nb : 4);
+  else
+    stage_b_tile(MX_BUF_B(0), wg, n0, ldw, 0, wave, lane);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
   for (int kt = 0; kt < KT; ++kt) {
     const int cur = kt & 1;
     unsigned nsc[4] = {0u, 0u, 0u, 0u};
+    unsigned fix_sh = 0u, fix_or = 0u;  // KRAG: applied to the next tile's scale dwords once landed
     if (kt + 1 < KT) {
-      stage_a_tile(MX_BUF_A(cur ^ 1), xg, m0, K, (long)(kt + 1) << 7, wave, lane);
-      stage_b_tile(MX_BUF_B(cur ^ 1), wg, n0, ldw, (long)(kt + 1) << 6, wave, lane);
+      stage_a_tile(MX_BUF_A(cur ^ 1), xg, m0, KA, (long)(kt + 1) << 7, wave, lane);
+      if (RAGGED) {
+        const bool lastn = KRAG && kt + 2 == KT;  // uniform: the next tile is the last
+        stage_b_tile_edge<KRAG>(MX_BUF_B(cur ^ 1), wg, n0, ldw, (long)(kt + 1) << 6, wave, lane,
+                                nl, lastn ? nb : 4);
+        // two tiles: bpr >= 5, so the dword that ends with the row starts in it
+        const char* sp = sbase + (lastn ? bpr - 4 : 4 * (kt + 1));
+        if (lastn && nb < 4) {
+          fix_sh = 8u * (unsigned)(4 - nb);
+          fix_or = 0x7f7f7f7fu << (8 * nb);
+        }
 #pragma unroll
-      for (int j = 0; j < 4; ++j) nsc[j] = srow[(long)j * 16 * KT + kt + 1];
+        for (int j = 0; j < 4; ++j) nsc[j] = load_u32_any(sp + so[j]);
+      } else {
+        stage_b_tile(MX_BUF_B(cur ^ 1), wg, n0, ldw, (long)(kt + 1) << 6, wave, lane);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) nsc[j] = srow[(long)j * 16 * KT + kt + 1];
+      }
     }
     const char* A = MX_BUF_A(cur);
     const char* B = MX_BUF_B(cur);
@@ -414,7 +515,7 @@ __global__ __launch_bounds__(512) void fused_mxfp4_gemm_kernel(
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 #pragma unroll
-    for (int j = 0; j < 4; ++j) sc[j] = nsc[j];
+    for (int j = 0; j < 4; ++j) sc[j] = KRAG ? (nsc[j] >> fix_sh) | fix_or : nsc[j];
   }
 
   // ---- 1. activation row scale on the resident accumulators (fp32) -------
@@ -437,7 +538,7 @@ __global__ __launch_bounds__(512) void fused_mxfp4_gemm_kernel(
 #pragma unroll 1
     for (int c = 0; c < RC; ++c) {
       stage_a_tile(TA, (const char*)t, m0, ldr, (long)c << 7, wave, lane);
-      stage_a_tile(TB, (const char*)bw, n0, ldr, (long)c << 7, wave, lane);
+      stage_a_tile<RAGGED>(TB, (const char*)bw, n0, ldr, (long)c << 7, wave, lane, nl);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
       __builtin_amdgcn_s_setprio(1);
@@ -465,7 +566,11 @@ __global__ __launch_bounds__(512) void fused_mxfp4_gemm_kernel(
   __bf16* mine = (__bf16*)smem + wave * (64 * 64);
   float bv[4];
 #pragma unroll
-  for (int j = 0; j < 4; ++j) bv[j] = bias ? (float)bias[n0 + wc * 64 + j * 16 + fr] : 0.f;
+  for (int j = 0; j < 4; ++j) {
+    long n = n0 + wc * 64 + j * 16 + fr;
+    if (RAGGED) n = n < nl ? n : nl;
+    bv[j] = bias ? (float)bias[n] : 0.f;
+  }
 #pragma unroll
   for (int half = 0; half < 2; ++half) {
 #pragma unroll
@@ -485,8 +590,24 @@ __global__ __launch_bounds__(512) void fused_mxfp4_gemm_kernel(
       const int row = rr * 8 + (lane >> 3);          // 0..63
       const int cb = (lane & 7) * 8;                 // 8-col chunk
       const bf16x8_m vv = *reinterpret_cast<const bf16x8_m*>(mine + row * 64 + cb);
-      *reinterpret_cast<bf16x8_m*>(y + (m0 + wr * 128 + half * 64 + row) * N + n0 + wc * 64 +
-                                   cb) = vv;
+      if (RAGGED) {
+        // pitch N: with N % 8 != 0 a row start is only 2-byte aligned, so the
+        // 16-byte store goes through Vec8 (alignof 2); the chunk that straddles
+        // N goes element by element, later ones are skipped
+        const long col = n0 + wc * 64 + cb;
+        __hip_bfloat16* dst = y + (m0 + wr * 128 + half * 64 + row) * N + col;
+        if (col + 8 <= N) {
+          store8(dst, *reinterpret_cast<const Vec8<__hip_bfloat16>*>(&vv));
+        } else {
+          const __hip_bfloat16* sv = reinterpret_cast<const __hip_bfloat16*>(&vv);
+#pragma unroll
+          for (int e = 0; e < 8; ++e)
+            if (col + e < N) dst[e] = sv[e];
+        }
+      } else {
+        *reinterpret_cast<bf16x8_m*>(y + (m0 + wr * 128 + half * 64 + row) * N + n0 + wc * 64 +
+                                     cb) = vv;
+      }
     }
     __builtin_amdgcn_wave_barrier();
   }
@@ -527,10 +648,70 @@ torch::Tensor fused_mxfp4_gemm(torch::Tensor xq, torch::Tensor xs, torch::Tensor
   auto y = torch::empty({M, N}, xq.options().dtype(torch::kBFloat16));
   auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
   dim3 grid((unsigned)((M >> 8) * (N >> 8))), block(512);
-  hipLaunchKernelGGL(fused_mxfp4_gemm_kernel, grid, block, MX_SMEM_BYTES, stream,
+  hipLaunchKernelGGL((fused_mxfp4_gemm_kernel<false, false>), grid, block, MX_SMEM_BYTES, stream,
                      xq.data_ptr<uint8_t>(), xs.data_ptr<float>(), wq.data_ptr<uint8_t>(),
                      (const unsigned*)wscales.data_ptr<uint8_t>(),
                      a.t, a.bw, a.bias, (__hip_bfloat16*)y.data_ptr(), M, N, K, a.r);
+  HIP_CHECK_LAST();
+  return y;
+}
+
+// one uint8 operand of fused_mxfp4_gemm_ragged; `align` 1 for none
+static void check_mx_u8_ragged(const char* fn, const char* what, const torch::Tensor& v,
+                               const torch::Device& dev, long numel, const char* count,
+                               int align) {
+  TORCH_CHECK(v.is_cuda() && v.device() == dev, fn, ": ", what, " must be on xq's GPU");
+  TORCH_CHECK(v.scalar_type() == torch::kUInt8, fn, ": ", what, " must be uint8");
+  TORCH_CHECK(v.is_contiguous(), fn, ": ", what, " must be contiguous");
+  TORCH_CHECK(v.numel() == numel, fn, ": ", what, " must hold ", count, " bytes");
+  TORCH_CHECK((uintptr_t)v.data_ptr() % align == 0, fn, ": ", what, " must be ", align,
+              "-byte aligned");
+}
+
+// fused_mxfp4_gemm for any N >= 1 and any K >= 1 (llama_1b's gate/up: N = 5461,
+// its down_proj: K = 5461); y has pitch N.  xq is [M, Kp128], Kp128 = K rounded
+// up to 128, its pad columns zero codes: quantize_rows_fp8 for K % 128 == 0,
+// quantize_rows_fp8_padded otherwise (the pad's contents are their contract,
+// not checked here).  wq / wscales as quantize_rows_mxfp4 returns them for a
+// [N,K] weight: N*Kp/2 and N*ceil(K/32) bytes, Kp = K rounded up to 32.  The
+// ragged kernels load scale dwords from any byte address, so wscales may start
+// anywhere; aligned N and K run the aligned kernel, which wants whole dwords.
+torch::Tensor fused_mxfp4_gemm_ragged(torch::Tensor xq, torch::Tensor xs, torch::Tensor wq,
+                                      torch::Tensor wscales, long N, long K, torch::Tensor t,
+                                      torch::Tensor bw, torch::Tensor bias, double lora_scale) {
+  const char* fn = "fused_mxfp4_gemm_ragged";
+  TORCH_CHECK(xq.is_cuda(), fn, ": xq must be a GPU tensor");
+  TORCH_CHECK(xq.dim() == 2, fn, ": xq must be 2-D [M, Kp128]");
+  const long M = xq.size(0);
+  TORCH_CHECK(M > 0 && K > 0 && N > 0, fn, ": M, N and K must be > 0");
+  TORCH_CHECK(M % 256 == 0, fn, " requires M%256==0");
+  TORCH_CHECK(K < (1L << 24) && N < (1L << 31) && (M >> 8) * ((N + 255) >> 8) < (1L << 31), fn,
+              ": shape too large");
+  const long KA = (K + 127) / 128 * 128, bpr = (K + MX_BLOCK - 1) / MX_BLOCK;
+  TORCH_CHECK(xq.size(1) == KA, fn, ": xq must have K rounded up to 128 columns");
+  const bool krag = K % 128 != 0, nrag = N % 256 != 0;
+  const auto dev = xq.device();
+  check_mx_u8_ragged(fn, "x codes", xq, dev, M * KA, "M*Kp128", 16);
+  TORCH_CHECK(xs.device() == dev, fn, ": x absmax must be on xq's device");
+  TORCH_CHECK(xs.scalar_type() == torch::kFloat32, fn, ": x absmax must be fp32");
+  TORCH_CHECK(xs.is_contiguous(), fn, ": x absmax must be contiguous");
+  TORCH_CHECK(xs.numel() == M, fn, ": x absmax must hold one value per row");
+  check_mx_u8_ragged(fn, "w codes", wq, dev, N * bpr * (MX_BLOCK / 2), "N*Kp/2", 16);
+  check_mx_u8_ragged(fn, "w scales", wscales, dev, N * bpr, "N*ceil(K/32)",
+                     krag || nrag ? 1 : 4);
+  const LoraArgs a = prep_lora_bias(fn, "xq", dev, t, bw, bias, M, N, 64, 256, lora_scale);
+  auto y = torch::empty({M, N}, xq.options().dtype(torch::kBFloat16));
+  auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
+  dim3 grid((unsigned)((M >> 8) * ((N + 255) >> 8))), block(512);
+#define LAUNCH_MX(RAG, KRAG)                                                                   \
+  hipLaunchKernelGGL((fused_mxfp4_gemm_kernel<RAG, KRAG>), grid, block, MX_SMEM_BYTES, stream, \
+                     xq.data_ptr<uint8_t>(), xs.data_ptr<float>(), wq.data_ptr<uint8_t>(),     \
+                     (const unsigned*)wscales.data_ptr<uint8_t>(), a.t, a.bw, a.bias,          \
+                     (__hip_bfloat16*)y.data_ptr(), M, N, K, a.r)
+  if (krag) LAUNCH_MX(true, true);
+  else if (nrag) LAUNCH_MX(true, false);
+  else LAUNCH_MX(false, false);
+#undef LAUNCH_MX
   HIP_CHECK_LAST();
   return y;
 }

@@ -820,6 +820,16 @@ _FP8_RAGGED = os.environ.get("RELORA_AMD_FP8_RAGGED", "1") != "0"
 _FP8_KRAGGED_FWD = True
 _FP8_KRAGGED_DX = True
 
+# MXFP4 frozen W whose out_features is no multiple of 256 or whose in_features
+# is no multiple of 128 (llama_1b's gate/up/down at 5461): fused_mxfp4_gemm_ragged
+# (ops/csrc/mxfp4_gemm.hip).  RELORA_AMD_MXFP4_RAGGED=0 sends those shapes back
+# to the materialize arm.
+_MXFP4_RAGGED = os.environ.get("RELORA_AMD_MXFP4_RAGGED", "1") != "0"
+# the two directions of raggedness, each dispatched where its measured A/B
+# favours it (docs/KERNELS.md "Ragged widths")
+_MXFP4_RAGGED_N = True
+_MXFP4_RAGGED_K = True
+
 
 class _QuantizedLoRALinear(torch.autograd.Function):
     """K15 path: frozen W stays NF4/int8/fp8/MXFP4-packed end to end.  Forward
@@ -889,6 +899,22 @@ class _QuantizedLoRALinear(torch.autograd.Function):
             xq, xs = hip.ext().quantize_rows_fp8(x2d)
             y = hip.ext().fused_mxfp4_gemm(
                 xq, xs, qw.qdata, qw.absmax, N, t_u, lora_B,
+                bias if bias is not None else empty, scale)
+            del xq, xs
+        elif (_MXFP4_RAGGED and qw.mode == "mxfp4" and M % 256 == 0 and r % 64 == 0
+              and r <= 256 and _FUSED_K1 != "0" and (K + 127) // 128 * 128 <= 8192
+              and ((K % 128 != 0 and _MXFP4_RAGGED_K)
+                   or (K % 128 == 0 and N % 256 != 0 and _MXFP4_RAGGED_N))):
+            # any N and K: edge block column clamped and rows of pitch N stored
+            # up to column N; for a ragged K the activation codes are padded
+            # with zero codes to whole 128-k tiles, W's code rows (pitch Kp/2)
+            # still come by glds and the last tile's missing blocks are clamped
+            if K % 128 != 0:
+                xq, xs = hip.ext().quantize_rows_fp8_padded(x2d)
+            else:
+                xq, xs = hip.ext().quantize_rows_fp8(x2d)
+            y = hip.ext().fused_mxfp4_gemm_ragged(
+                xq, xs, qw.qdata, qw.absmax, N, K, t_u, lora_B,
                 bias if bias is not None else empty, scale)
             del xq, xs
         elif fused_nf4:

@@ -20,9 +20,10 @@ MI355X notes:
 * `quantize="fp8"` stores e4m3 codes with one scale per output row and, on
   aligned shapes, multiplies on the codes directly (ops/csrc/fp8_gemm.hip);
 * `quantize="mxfp4"` stores OCP MXFP4 blocks (e2m1 codes, one E8M0 scale per
-  32 elements of a row) and, on aligned shapes, multiplies e4m3 activations
-  with the stored codes on the block-scaled matrix instructions
-  (ops/csrc/mxfp4_gemm.hip).
+  32 elements of a row) and, for token counts that are multiples of 256 and
+  in_features up to 8192, multiplies e4m3 activations with the stored codes
+  on the block-scaled matrix instructions, at any out_features and
+  in_features (llama_1b's 5461 included; ops/csrc/mxfp4_gemm.hip).
 """
 
 import json
