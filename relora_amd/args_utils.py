@@ -145,6 +145,13 @@ def check_args_torchrun_main(args, n_cli_args=None):
     if args.fp8_backward and getattr(args, "quantize", None) != "fp8":
         raise ValueError("--fp8_backward true needs --quantize fp8")
 
+    mx_bwd = getattr(args, "mxfp4_backward", False)
+    if isinstance(mx_bwd, str):  # YAML
+        mx_bwd = mx_bwd.lower() == "true"
+    args.mxfp4_backward = bool(mx_bwd)
+    if args.mxfp4_backward and getattr(args, "quantize", None) != "mxfp4":
+        raise ValueError("--mxfp4_backward true needs --quantize mxfp4")
+
     if getattr(args, "intra_doc_masking", False) and _is_pythia_run(args):
         raise ValueError(
             "--intra_doc_masking is implemented for the LLaMA models only; "

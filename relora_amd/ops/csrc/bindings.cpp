@@ -141,6 +141,8 @@ torch::Tensor fused_mxfp4_gemm(torch::Tensor xq, torch::Tensor xs, torch::Tensor
 torch::Tensor fused_mxfp4_gemm_ragged(torch::Tensor xq, torch::Tensor xs, torch::Tensor wq,
                                       torch::Tensor wscales, long N, long K, torch::Tensor t,
                                       torch::Tensor bw, torch::Tensor bias, double lora_scale);
+torch::Tensor fused_mxfp4_gemm_dx(torch::Tensor gq, torch::Tensor gs, torch::Tensor wq,
+                                  torch::Tensor wscales, torch::Tensor emax, long N, long K);
 // attention.hip
 std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor v,
                                     double scale, c10::optional<torch::Tensor> doc_start);
@@ -299,6 +301,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "missing blocks of a row's last tile clamped and scaled by 2^0 (gfx950)",
         py::arg("xq"), py::arg("xs"), py::arg("wq"), py::arg("wscales"), py::arg("N"),
         py::arg("K"), py::arg("t"), py::arg("bw"), py::arg("bias"), py::arg("lora_scale"));
+  // gq / gs: quantize_rows_fp8(dy); emax: the largest scale byte of every 32-column stripe
+  m.def("fused_mxfp4_gemm_dx", &fused_mxfp4_gemm_dx,
+        "dx = (gq@B)*sg*2^(E-133), bf16 [M,K]: W's MXFP4 codes transcoded to e4m3 against the "
+        "stripe exponent E while staged, unscaled fp8 f8f6f4 MFMA, 256^2 tile (gfx950)",
+        py::arg("gq"), py::arg("gs"), py::arg("wq"), py::arg("wscales"), py::arg("emax"),
+        py::arg("N"), py::arg("K"));
   // doc_start: optional int32 [B, S] intra-document mask (padded head_dim <= 64)
   m.def("attn_fwd", &attn_fwd, "causal flash attention forward (gfx950 MFMA)",
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("scale"),

@@ -26,6 +26,8 @@
 //                          xq/xs from quantize_rows_fp8, W4 as stored
 //   ..._ragged             any N (out_features) and any K (in_features): xq/xs
 //                          from quantize_rows_fp8_padded when K % 128 != 0
+//   fused_mxfp4_gemm_dx    dx = dy @ W on the fp8 cores, W transcoded to e4m3
+//                          per stripe while staged (at the end of this file)
 //
 // GEMM structure: fused_fp8_gemm's 256x256 tile, 8 waves (2M x 4N),
 // double-buffered global_load_lds staging, XCD remap and one vmcnt(0) +
@@ -714,6 +716,279 @@ torch::Tensor fused_mxfp4_gemm_ragged(torch::Tensor xq, torch::Tensor xs, torch:
 #undef LAUNCH_MX
   HIP_CHECK_LAST();
   return y;
+}
+
+// ---------------------------------------------------------------------------
+// fused_mxfp4_gemm_dx: dx = dy @ W from W's MXFP4 codes, on the fp8 cores.
+//
+// W's block scales run along k within a row n and dx reduces over n, so a
+// scale is no factor of an output, cannot be folded into dy and is no block
+// scale along the reduction.  Instead W is transcoded to e4m3 while it is
+// staged, against one exponent per stripe (the 32 columns of an MX block
+// column): E[kb] = max_n s[n,kb] comes from the host, and
+//   B[n,k]  = e4m3_rne(e2m1(code[n,k]) * 2^(s[n,kb] - E[kb] + 6))
+//   dx[m,k] = (sum_n g[m,n] B[n,k]) * (gs[m]/448) * 2^(E[kb] - 133)
+// (ops/quant.py transcode_mxfp4_e4m3_ref is the definition).  B is exact up
+// to a spread E - s of 14, |B| <= 384, no NaN code arises.
+//
+// Geometry of fused_fp8_gemm_dx (fp8_gemm.hip): 256x256 tile over [M,K], 8
+// waves 2x4, XCD remap, 128-n reduction tiles, A = gq by glds into the swz_a
+// image, double buffer, one vmcnt(0) + barrier per tile, the unscaled
+// 16x16x128 f8f6f4 MFMA on two e4m3 operands (fragment chunks fq and 4+fq, the
+// lane-to-k order the read-back tests found), a [256 k][128 n] byte B image
+// under swz_a read by frag_e4m3, b128 row stores through LDS.
+//
+// The B stager.  A reduction tile of W is 128 rows x 128 bytes (256 k as
+// nibbles, row pitch K/2).  A thread owns the 16 n x 4 k patch of fp8_gemm's
+// dx kernel (k-quad q = l[1:0] | l[5:3]<<2 | w[0]<<5, n-chunk c = 2*w[2:1] +
+// l[2]): 16 two-byte loads of codes and 16 one-byte loads of scales (4 k lie in
+// one MX block: a byte per patch row, pitch K/32), issued one tile ahead right
+// after A's glds and in flight during the 32 MFMAs.  A wave's code load covers
+// 2 rows x 64 contiguous bytes.  (The 8 n x 8 k patch would load whole 128-byte
+// rows, but its eight b64 writes of a 16-lane group fall on two swizzle values
+// of one 8-byte column: 8-way.)  Behind the MFMAs each row's four nibbles go
+// through v_cvt_scalef32_pk_f32_fp4 with the scale 2^(s - E + 6) (exact) and
+// v_cvt_pk_fp8_f32 (the RNE, subnormals and signed zero of the definition):
+// one dword W[n][4 k] of e4m3 bytes, 5 VALU a row.  From there on it is the
+// fp8 patch: a byte transposition of four 4x4 blocks by v_perm_b32 and four
+// b128 writes, conflict-free (tools/lds_bank_model.py mxfp4_dx_patch_writes).
+// The stripe's E costs a thread one byte load for its patch and two for its
+// accumulator columns (64 columns of a wave = 2 stripes).
+// ---------------------------------------------------------------------------
+
+#define MXDX_TILE_BYTES (256 * 128)
+#define MXDX_BUF_A(b) (smem + (b) * (2 * MXDX_TILE_BYTES))
+#define MXDX_BUF_B(b) (smem + (b) * (2 * MXDX_TILE_BYTES) + MXDX_TILE_BYTES)
+#define MXDX_SMEM_BYTES (4 * MXDX_TILE_BYTES)  // 128 KiB
+
+typedef __attribute__((ext_vector_type(2))) float f32x2_m;
+
+// issue the loads of this thread's patch of one W reduction tile: `codes`
+// points at the codes of W[n_tile0][k0], `scl` at the scale byte of that
+// block (both uniform), `vo` / `so` are the lane's byte offsets
+DEV_INLINE void load_w4_patch(unsigned (&st)[16], unsigned (&sc)[16], const char* codes,
+                              const uint8_t* scl, long ldw, long bpr, unsigned vo, unsigned so) {
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    st[i] = *reinterpret_cast<const unsigned short*>(codes + (long)i * ldw + vo);
+    sc[i] = scl[(long)i * bpr + so];
+  }
+}
+
+// st[i]: four e2m1 codes W[n = 16c + i][k = 4q .. 4q+3] (low nibble first) ->
+// their four e4m3 bytes at 2^(s - E + 6).  The spread E - s is clamped to
+// 0..32: from 19 on every byte is a zero, and the scale stays a normal fp32.
+DEV_INLINE void transcode_w4_patch(unsigned (&st)[16], const unsigned (&sc)[16], unsigned e) {
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const int spread = min(max((int)e - (int)sc[i], 0), 32);
+    const float f = __uint_as_float((unsigned)(133 - spread) << 23);
+    const f32x2_m lo = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(st[i], f, 0);
+    const f32x2_m hi = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(st[i], f, 1);
+    int p = __builtin_amdgcn_cvt_pk_fp8_f32(lo[0], lo[1], 0, false);
+    p = __builtin_amdgcn_cvt_pk_fp8_f32(hi[0], hi[1], p, true);
+    st[i] = (unsigned)p;
+  }
+}
+
+// st[i] holds B[n = 16c + i][k = 4q .. 4q+3]; write image rows 4q..4q+3,
+// 16-byte chunk c (n = 16c .. 16c+15 ascending): fp8_gemm's write_b_patch
+DEV_INLINE void write_bt_patch(char* image, const unsigned (&st)[16], int pq, int pc) {
+  unsigned o[4][4];
+#pragma unroll
+  for (int b = 0; b < 4; ++b) {
+    const unsigned lo01 = __builtin_amdgcn_perm(st[4 * b + 1], st[4 * b + 0], 0x05010400u);
+    const unsigned hi01 = __builtin_amdgcn_perm(st[4 * b + 1], st[4 * b + 0], 0x07030602u);
+    const unsigned lo23 = __builtin_amdgcn_perm(st[4 * b + 3], st[4 * b + 2], 0x05010400u);
+    const unsigned hi23 = __builtin_amdgcn_perm(st[4 * b + 3], st[4 * b + 2], 0x07030602u);
+    o[0][b] = __builtin_amdgcn_perm(lo23, lo01, 0x05040100u);
+    o[1][b] = __builtin_amdgcn_perm(lo23, lo01, 0x07060302u);
+    o[2][b] = __builtin_amdgcn_perm(hi23, hi01, 0x05040100u);
+    o[3][b] = __builtin_amdgcn_perm(hi23, hi01, 0x07060302u);
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const unsigned p = swz_a((unsigned)(4 * pq + j) * 128u + (unsigned)pc * 16u);
+    *reinterpret_cast<i32x4_m*>(image + p) =
+        i32x4_m{(int)o[j][0], (int)o[j][1], (int)o[j][2], (int)o[j][3]};
+  }
+}
+
+__global__ __launch_bounds__(512) void fused_mxfp4_gemm_dx_kernel(
+    const uint8_t* __restrict__ gq,    // [M,N] e4m3 codes of dy
+    const float* __restrict__ ga,      // [M] absmax of its rows
+    const uint8_t* __restrict__ wq,    // [N,K/2] e2m1 codes of W
+    const uint8_t* __restrict__ wsc,   // [N,K/32] E8M0 block scales
+    const uint8_t* __restrict__ emax,  // [K/32] largest scale byte of each stripe
+    __hip_bfloat16* __restrict__ dx,   // [M,K]
+    long M, long N, long K) {
+  // one __shared__ array only (glds pipeline rule)
+  extern __shared__ __attribute__((aligned(16))) char smem[];  // [2][A | B] = 128 KiB
+
+  // XCD-aware blockIdx remap (bijective form), as in fused_mxfp4_gemm_kernel
+  const int nwg = gridDim.x;
+  const int q8 = nwg >> 3, r8 = nwg & 7;
+  int wgid = blockIdx.x;
+  if (nwg >= 8) {
+    const int xcd = wgid & 7, pos = wgid >> 3;
+    wgid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + pos;
+  }
+  const int nbk = (int)(K >> 8);
+  const long m0 = (long)(wgid / nbk) << 8;
+  const long k0 = (long)(wgid % nbk) << 8;
+
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int wr = wave >> 2;   // 0..1: wave m-position (128 rows)
+  const int wc = wave & 3;    // 0..3: wave k-position (64 cols)
+  const int fr = lane & 15;   // fragment row / C column
+  const int fq = lane >> 4;   // fragment n-group / C row group
+
+  // this thread's patch of every W tile
+  const int pq = (lane & 3) | ((lane >> 3) << 2) | ((wave & 1) << 5);
+  const int pc = (wave >> 1) * 2 + ((lane >> 2) & 1);
+  const long ldw = K >> 1;  // code row pitch in bytes
+  const long bpr = K >> 5;  // scale bytes per row
+  // 32-bit lane offsets next to scalar row bases: 127 * K/2 + 126 < 2^30
+  const unsigned voff = (unsigned)(pc * 16) * (unsigned)ldw + (unsigned)(pq * 2);
+  const unsigned soff = (unsigned)(pc * 16) * (unsigned)bpr + (unsigned)(pq >> 3);
+  const uint8_t* eb = emax + (k0 >> 5);   // the block's 8 stripes
+  const unsigned ep = eb[pq >> 3];        // the patch's stripe
+
+  f32x4_m acc[8][4];
+#pragma unroll
+  for (int i = 0; i < 8; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_m{0.f, 0.f, 0.f, 0.f};
+
+  const char* gg = (const char*)gq;
+  const char* wg = (const char*)wq + (k0 >> 1);
+  const uint8_t* sg8 = wsc + (k0 >> 5);
+  const int NT = (int)(N >> 7);  // 128-n tiles
+  unsigned st[16], sc[16];
+
+  stage_a_tile(MXDX_BUF_A(0), gg, m0, N, 0, wave, lane);
+  load_w4_patch(st, sc, wg, sg8, ldw, bpr, voff, soff);
+  transcode_w4_patch(st, sc, ep);
+  write_bt_patch(MXDX_BUF_B(0), st, pq, pc);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+
+  for (int nt = 0; nt < NT; ++nt) {
+    const int cur = nt & 1;
+    const bool more = nt + 1 < NT;
+    if (more) {
+      stage_a_tile(MXDX_BUF_A(cur ^ 1), gg, m0, N, (long)(nt + 1) << 7, wave, lane);
+      // keep the lane offsets opaque 32-bit VGPRs (saddr form): hoisted out
+      // of the loop they become 32 64-bit lane addresses
+      unsigned vo = voff, so = soff;
+      asm volatile("" : "+v"(vo), "+v"(so));
+      load_w4_patch(st, sc, wg + ((long)(nt + 1) << 7) * ldw, sg8 + ((long)(nt + 1) << 7) * bpr,
+                    ldw, bpr, vo, so);
+    }
+    const char* A = MXDX_BUF_A(cur);
+    const char* B = MXDX_BUF_B(cur);
+    __builtin_amdgcn_s_setprio(1);
+    // the 4 B fragments stay resident (32 VGPRs); A fragments stream through
+    i32x8_m bf[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) bf[j] = frag_e4m3(B, wc * 64 + j * 16 + fr, fq);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const i32x8_m af = frag_e4m3(A, wr * 128 + i * 16 + fr, fq);
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
+            af, bf[j], acc[i][j], 0 /*A e4m3*/, 0 /*B e4m3*/, 0, 0, 0, 0);
+    }
+    __builtin_amdgcn_s_setprio(0);
+    // the other B image was last read in the previous iteration, behind its
+    // barrier; the patch loads had the whole MFMA loop to land
+    if (more) {
+      transcode_w4_patch(st, sc, ep);
+      write_bt_patch(MXDX_BUF_B(cur ^ 1), st, pq, pc);
+    }
+    // drain next tile's glds, then release the buffers we just read
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+  }
+
+  // ---- gs[m]/448, then the stripe's power of two applied exactly (ldexp);
+  // a wave's 64 columns are two stripes, column fragments 0-1 and 2-3
+  const int e2[2] = {(int)eb[wc * 2] - 133, (int)eb[wc * 2 + 1] - 133};
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const f32x4_m ax = *reinterpret_cast<const f32x4_m*>(ga + m0 + wr * 128 + i * 16 + fq * 4);
+    const f32x4_m sg = {__fdiv_rn(ax[0], E4M3_MAX), __fdiv_rn(ax[1], E4M3_MAX),
+                        __fdiv_rn(ax[2], E4M3_MAX), __fdiv_rn(ax[3], E4M3_MAX)};
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg)
+        acc[i][j][reg] = ldexpf(__fmul_rn(acc[i][j][reg], sg[reg]), e2[j >> 1]);
+  }
+  // ---- one bf16 rounding, b128 row stores through LDS (16 KiB per wave)
+  __bf16* mine = (__bf16*)smem + wave * (128 * 64);
+#pragma unroll
+  for (int i = 0; i < 8; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg)
+        mine[(i * 16 + fq * 4 + reg) * 64 + j * 16 + fr] = (__bf16)acc[i][j][reg];
+  // no barrier needed: each wave reads only its own region
+#pragma unroll
+  for (int rr = 0; rr < 16; ++rr) {
+    const int row = rr * 8 + (lane >> 3);          // 0..127
+    const int cb = (lane & 7) * 8;                 // 8-col chunk
+    const bf16x8_m vv = *reinterpret_cast<const bf16x8_m*>(mine + row * 64 + cb);
+    *reinterpret_cast<bf16x8_m*>(dx + (m0 + wr * 128 + row) * K + k0 + wc * 64 + cb) = vv;
+  }
+}
+
+// one uint8 operand of fused_mxfp4_gemm_dx; `align` 1 for none
+static void check_mx_dx_u8(const char* fn, const char* what, const torch::Tensor& v,
+                           const torch::Device& dev, long numel, const char* count, int align) {
+  TORCH_CHECK(v.is_cuda() && v.device() == dev, fn, ": ", what, " must be on gq's GPU");
+  TORCH_CHECK(v.scalar_type() == torch::kUInt8, fn, ": ", what, " must be uint8");
+  TORCH_CHECK(v.is_contiguous(), fn, ": ", what, " must be contiguous");
+  TORCH_CHECK(v.numel() == numel, fn, ": ", what, " must hold ", count, " bytes");
+  TORCH_CHECK((uintptr_t)v.data_ptr() % align == 0, fn, ": ", what, " must be ", align,
+              "-byte aligned");
+}
+
+// gq / gs: quantize_rows_fp8(dy) [M,N]; wq / wscales as stored for a [N,K]
+// weight; emax [K/32]: the column maximum of wscales.  The kernel indexes from
+// M, N and K alone, so every size is checked against them here.
+torch::Tensor fused_mxfp4_gemm_dx(torch::Tensor gq, torch::Tensor gs, torch::Tensor wq,
+                                  torch::Tensor wscales, torch::Tensor emax, long N, long K) {
+  const char* fn = "fused_mxfp4_gemm_dx";
+  TORCH_CHECK(gq.is_cuda(), fn, ": gq must be a GPU tensor");
+  TORCH_CHECK(gq.dim() == 2, fn, ": gq must be 2-D [M, N]");
+  const long M = gq.size(0);
+  TORCH_CHECK(M > 0 && N > 0 && K > 0, fn, ": M, N and K must be > 0");
+  TORCH_CHECK(M % 256 == 0 && K % 256 == 0 && N % 128 == 0, fn,
+              " requires M%256==0, K%256==0, N%128==0");
+  TORCH_CHECK(K < (1L << 24) && N < (1L << 31) && (M >> 8) * (K >> 8) < (1L << 31), fn,
+              ": shape too large");
+  const auto dev = gq.device();
+  check_mx_dx_u8(fn, "g codes", gq, dev, M * N, "M*N", 16);
+  TORCH_CHECK(gs.device() == dev, fn, ": g absmax must be on gq's device");
+  TORCH_CHECK(gs.scalar_type() == torch::kFloat32, fn, ": g absmax must be fp32");
+  TORCH_CHECK(gs.is_contiguous(), fn, ": g absmax must be contiguous");
+  TORCH_CHECK(gs.dim() == 1 && gs.numel() == M, fn, ": g absmax must hold one value per row");
+  check_mx_dx_u8(fn, "w codes", wq, dev, N * K / 2, "N*K/2", 16);
+  check_mx_dx_u8(fn, "w scales", wscales, dev, N * K / MX_BLOCK, "N*K/32", 1);
+  check_mx_dx_u8(fn, "stripe exponents", emax, dev, K / MX_BLOCK, "K/32", 1);
+  auto dx = torch::empty({M, K}, gq.options().dtype(torch::kBFloat16));
+  auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
+  dim3 grid((unsigned)((M >> 8) * (K >> 8))), block(512);
+  hipLaunchKernelGGL(fused_mxfp4_gemm_dx_kernel, grid, block, MXDX_SMEM_BYTES, stream,
+                     gq.data_ptr<uint8_t>(), gs.data_ptr<float>(), wq.data_ptr<uint8_t>(),
+                     wscales.data_ptr<uint8_t>(), emax.data_ptr<uint8_t>(),
+                     (__hip_bfloat16*)dx.data_ptr(), M, N, K);
+  HIP_CHECK_LAST();
+  return dx;
 }
 
 #if defined(__HIP_DEVICE_COMPILE__)

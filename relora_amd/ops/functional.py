@@ -970,6 +970,15 @@ class _QuantizedLoRALinear(torch.autograd.Function):
             gq, gs = hip.ext().quantize_rows_fp8_scaled_padded(dy2d, qw.absmax)
             dx = hip.ext().fused_fp8_gemm_dx_kragged(gq, gs, qw.qdata, N, K)
             del gq, gs
+        elif (ctx.fp8_backward and qw.mode == "mxfp4" and M % 256 == 0 and K % 256 == 0
+                and N % 128 == 0 and _FUSED_K1 != "0"):
+            # opt-in: dy quantised per token row, W's MXFP4 codes transcoded to
+            # e4m3 against the largest scale byte of each 32-column stripe while
+            # they are staged (no dense W), the stripe's power of two applied
+            # to the accumulators
+            gq, gs = hip.ext().quantize_rows_fp8(dy2d)
+            dx = hip.ext().fused_mxfp4_gemm_dx(gq, gs, qw.qdata, qw.absmax, qw.stripe_emax(), N, K)
+            del gq, gs
         else:
             w = qw.materialize(torch.bfloat16)  # transient dense W for dX only
             dx = dy2d @ w
@@ -1038,10 +1047,12 @@ def lora_linear(x, weight, bias, lora_A, lora_B, scale, dropout_p=0.0,
     already passed through tanh by the caller) — tensor scale uses the
     composed path so autograd reaches it.
 
-    `fp8_backward` (fp8-quantized W on the GPU path only; ignored elsewhere):
-    the input gradient of aligned shapes runs on W's e4m3 codes with the
-    scaled gradient rounded to e4m3 per token row, instead of on a transient
-    bf16 W.
+    `fp8_backward` (fp8- or MXFP4-quantized W on the GPU path only; ignored
+    elsewhere): dx on the 8-bit matrix cores.  The input gradient of aligned
+    shapes runs on W's e4m3 codes with the scaled gradient rounded to e4m3 per
+    token row (fp8), or on W's MXFP4 codes transcoded to e4m3 tile by tile
+    with the gradient rounded to e4m3 per token row (mxfp4), instead of on a
+    transient bf16 W.
     """
     if quantized_weight is not None:
         if (hip.use_hip(x, "lora") and not lora_only and not torch.is_tensor(scale)

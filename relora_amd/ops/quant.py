@@ -167,6 +167,35 @@ def dequantize_mxfp4_ref(codes, scales, K, dtype=torch.float32):
     return out.view(N, -1)[:, :K].to(dtype)
 
 
+def transcode_mxfp4_e4m3_ref(codes, scales, K):
+    """python oracle and definition of the MXFP4 backward's B operand:
+    (codes [N, K/2], scales [N, K/32]) -> (B uint8 [N, K], E uint8 [K/32]).
+
+    A stripe is one MX block column: the 32 columns k = 32kb .. 32kb+31 over
+    all N rows.  E[kb] = max_n scales[n, kb], and
+        B[n, k] = e4m3_rne(e2m1(code[n, k]) * 2^(scales[n, kb] - E[kb] + 6)),
+    so that W[n, k] = e4m3(B[n, k]) * 2^(E[kb] - 133) wherever B is exact.
+    The stripe's largest block lands on 6 * 2^6 = 384 <= 448: no NaN code
+    arises.  Every e2m1 magnitude is a multiple of 0.5 and e4m3's subnormal
+    step is 2^-9, so B is exact while E - s <= 14; at 15 .. 18 the smallest
+    magnitudes round (ties to even) and from 19 on every code is a zero.  The
+    sign bit is kept throughout (-0 stays -0).  K % 32 == 0."""
+    N = codes.shape[0]
+    if K % MX_BLOCK or codes.shape != (N, K // 2) or scales.shape != (N, K // MX_BLOCK):
+        raise ValueError(f"need K % 32 == 0, codes [N, K/2] and scales [N, K/32]; got K={K}, "
+                         f"{tuple(codes.shape)} and {tuple(scales.shape)}")
+    c = torch.stack((codes & 0xF, codes >> 4), dim=2).view(N, K).long()
+    mag = E2M1_VALUES.to(codes.device)[c & 7]
+    val = torch.where((c & 8) != 0, -mag, mag)
+    emax = scales.amax(dim=0)
+    # 2^(s - E + 6): the exponent field 133 - (E - s); past a spread of 32
+    # everything is flushed anyway, and the field stays that of a normal fp32
+    spread = (emax.to(torch.int32).unsqueeze(0) - scales.to(torch.int32)).clamp(max=32)
+    factor = ((133 - spread) << 23).view(torch.float32)
+    b = (val.view(N, -1, MX_BLOCK) * factor.unsqueeze(2)).to(torch.float8_e4m3fn)
+    return b.view(torch.uint8).view(N, K).contiguous(), emax.contiguous()
+
+
 class QuantizedWeight(nn.Module):
     """A frozen 2-D weight stored quantized (blockwise NF4/int8, row-wise fp8,
     MXFP4 blocks along K).
@@ -187,7 +216,18 @@ class QuantizedWeight(nn.Module):
         self.dtype = weight.dtype
         self._encode(weight.detach())
 
+    def stripe_emax(self):
+        """mxfp4: E uint8 [K/32], the largest scale byte of every block column
+        (transcode_mxfp4_e4m3_ref).  Cached as a plain attribute, so it is no
+        state_dict key; a re-encode drops it, and a device move or an in-place
+        load of the scales (load_state_dict) recomputes it."""
+        key = (self.absmax.data_ptr(), self.absmax._version)
+        if self._emax is None or self._emax[0] != key:
+            self._emax = (key, self.absmax.amax(dim=0).contiguous())
+        return self._emax[1]
+
     def _encode(self, w):
+        self._emax = None
         if self.mode == "fp8":
             # qdata uint8 [N*K], absmax fp32 [N]: same buffer names as the
             # blockwise modes, so casts and checkpoints treat them alike

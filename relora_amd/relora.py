@@ -178,10 +178,14 @@ class ReLoRaModel(torch.nn.Module):
         return self
 
     def set_fp8_backward(self, enabled=True):
-        """Runtime switch of every ReLoRaLinear: with `quantize="fp8"` on the
-        GPU, aligned layers compute the input gradient on W's e4m3 codes (the
-        scaled output gradient is rounded to e4m3 per token row).  Not part of
-        relora_config.json; other modes, CPU and unaligned shapes ignore it."""
+        """Runtime switch of every ReLoRaLinear: dx on the 8-bit matrix cores.
+        With `quantize="fp8"` on the GPU, aligned layers compute the input
+        gradient on W's e4m3 codes (the scaled output gradient is rounded to
+        e4m3 per token row); with `quantize="mxfp4"`, on W's MXFP4 codes
+        transcoded to e4m3 tile by tile (the output gradient is rounded to
+        e4m3 per token row, W is used exactly up to a 2^14 spread of block
+        scales within 32 columns).  Not part of relora_config.json; other
+        modes, CPU and unaligned shapes ignore it."""
         for module in self.modules():
             if isinstance(module, ReLoRaLinear):
                 module.fp8_backward = bool(enabled)

@@ -159,6 +159,10 @@ def parse_args(args=None):
     parser.add_argument("--fp8_backward", default=False, type=lambda x: x.lower() == "true",
                         help="with --quantize fp8: input gradients of aligned linears on the "
                              "fp8 matrix cores (rounds the scaled output gradient to e4m3)")
+    parser.add_argument("--mxfp4_backward", default=False, type=lambda x: x.lower() == "true",
+                        help="with --quantize mxfp4: input gradients of aligned linears on the "
+                             "fp8 matrix cores, W transcoded from its MXFP4 codes tile by tile "
+                             "(rounds the output gradient to e4m3)")
 
     parser.add_argument("--distributed_type", type=str, default="ddp", choices=["fsdp", "ddp"])
     parser.add_argument("--profile", default=False, type=lambda x: x.lower() == "true")
@@ -606,6 +610,10 @@ def main(args):
         if args.fp8_backward:
             model.set_fp8_backward(True)
             logger.info("fp8 backward: input gradients of aligned fp8 linears on the e4m3 codes")
+        if args.mxfp4_backward:
+            model.set_fp8_backward(True)
+            logger.info("mxfp4 backward: input gradients of aligned MXFP4 linears on the fp8 "
+                        "matrix cores")
 
     if args.resume_from:
         logger.info(f"Loading model from {args.resume_from}")

@@ -465,3 +465,37 @@ if __name__ == "__main__":
         ok, ways = verify(fp8_kragged_b_writes(fn), "write_b128")
         print(f"fp8_gemm_kragged B chunk writes, {name}: {'conflict-free' if ok else f'{ways}-way'}")
     assert fp8_kragged_cover() == [(r, c) for r in range(256) for c in range(8)]
+
+
+# ---------------------------------------------------------------------------
+# fused_mxfp4_gemm_dx (mxfp4_gemm.hip): W's e2m1 nibbles are transcoded to e4m3
+# bytes in registers and written into the same [256 k][128 n] image.  The
+# kernel takes fp8_dx_patch (16 n x 4 k: 16 two-byte loads, four b128 stores).
+# The other patch shape on offer, 8 n x 8 k from 8 dword loads with whole
+# 128-byte rows per wave load (k-oct o = lane&31, n-oct c8 = 2*wave + lane>>5),
+# stores eight b64 rows 8o..8o+7 at byte 8*c8: a 16-lane group then writes 16
+# rows of one 8-byte column, which the swizzle spreads over two chunks only.
+# ---------------------------------------------------------------------------
+
+mxfp4_dx_patch = fp8_dx_patch
+
+
+def mxfp4_dx_patch_writes():
+    """every b128 write of one transcoded B image: the fp8 dx pattern."""
+    return fp8_dx_patch_writes(mxfp4_dx_patch)
+
+
+def mxfp4_dx_oct_writes():
+    """the rejected 8 n x 8 k patch: every b64 write of one B image."""
+    for wave in range(8):
+        for j in range(8):
+            yield {lane: fp8_gemm_swz((8 * (lane & 31) + j) * 128 + (2 * wave + (lane >> 5)) * 8)
+                   for lane in range(64)}
+
+
+if __name__ == "__main__":
+    for name, pats, kind in (("kernel (16n x 4k, b128)", mxfp4_dx_patch_writes(), "write_b128"),
+                             ("8n x 8k, b64", mxfp4_dx_oct_writes(), "write_b64")):
+        ok, ways = verify(pats, kind)
+        print(f"mxfp4_gemm_dx patch writes, {name}: {'conflict-free' if ok else f'{ways}-way'}")
+    assert fp8_dx_patch_cover(mxfp4_dx_patch) == [(q, c) for q in range(64) for c in range(8)]
